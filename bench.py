@@ -10,6 +10,11 @@ Each timed step is the full reference hot loop
 fused stage kernel, the host Friedmann update, halo exchange +
 fused grad/lap stencil, and the ⟨ρ⟩/⟨P⟩ energy reduction + allreduce.
 Synthetic random-init fields (no dataset exists for this workload).
+
+A plain run sets up, warms up, times ``--steps`` steps and prints one
+JSON result line.  ``--dump-outputs DIR`` additionally writes what the
+timed loop computed in its last step; ``--full`` is where secondary
+measurements and checks belong (none exist today).
 """
 
 import argparse
@@ -32,7 +37,48 @@ def proc_shape_for(n):
     return (n, 1, 1)
 
 
-def main():
+DUMP_BYTES = 32 * 2**20     # budget for the dumped field arrays
+STATE_KEYS = ("a", "adot", "hubble", "energy", "pressure")
+
+
+def dump_outputs(out_dir, arrays, state, h, decomp):
+    """Write the evolved arrays (everything the stepper updates; the
+    ``*_next`` ping-pong scratch is not an output) and the expansion
+    state as ``out_dir/<name>.npy`` in float64.  Interior sites only.
+    When the interior does not fit the byte budget, every array is
+    sampled at the same sites, drawn once from a fixed seed, so two
+    runs with the same arguments write comparable files."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{decomp.rank}" if decomp.nranks > 1 else ""
+    names = sorted(k for k, v in arrays.items()
+                   if not k.endswith("_next") and v.ndim >= 4
+                   and not k.startswith(("lap_", "dfdx")))
+    ncomp = sum(int(np.prod(arrays[k].shape[:-3])) for k in names)
+    first = arrays[names[0]]
+    rank_shape = tuple(n - 2 * h for n in first.shape[-3:])
+    nsites = int(np.prod(rank_shape))
+    nsample = DUMP_BYTES // (8 * ncomp)
+    idx = None
+    if nsites > nsample:
+        rng = np.random.default_rng(20240917)
+        flat = np.sort(rng.integers(0, nsites, size=nsample))
+        idx = tuple(torch.from_numpy(i + h).to(first.device)
+                    for i in np.unravel_index(flat, rank_shape))
+    for name in names:
+        arr = arrays[name]
+        if idx is None:
+            out = arr[(Ellipsis,) + tuple(slice(h, h + n)
+                                          for n in rank_shape)]
+        else:
+            out = arr[(Ellipsis,) + idx]
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"),
+                out.to(torch.float64).cpu().numpy())
+    np.save(os.path.join(out_dir, f"state{suffix}.npy"),
+            np.array([float(np.asarray(state[k]).reshape(-1)[0])
+                      for k in STATE_KEYS], dtype=np.float64))
+
+
+def main(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument("--gpus", type=int, default=1)
     parser.add_argument("--steps", type=int, default=20)
@@ -65,7 +111,19 @@ def main():
                         help="run the Friedmann (a, adot) update on the "
                              "host (one sync per RK stage) instead of "
                              "on-device")
-    p = parser.parse_args()
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps, write the evolved "
+                             "arrays of the last step (a fixed seeded "
+                             "sample of the interior sites when the "
+                             "grid is large) and the expansion state "
+                             "to DIR/<name>.npy as float64")
+    parser.add_argument("--full", action="store_true",
+                        help="also run the secondary measurements and "
+                             "checks (anything beyond the headline "
+                             "figure belongs behind this flag; there "
+                             "are none at present, so the run is the "
+                             "same as a plain one)")
+    p = parser.parse_args(argv)
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     if world_size > 1:
@@ -284,6 +342,15 @@ def main():
         final_energy = float(np.asarray(energy["total"]).reshape(-1)[0])
     assert np.isfinite(final_energy), \
         f"run diverged: energy={final_energy}"
+
+    if p.dump_outputs:
+        if device_loop is not None:
+            state = device_loop.read_state()
+        else:
+            state = {"a": expand.a, "adot": expand.adot,
+                     "hubble": expand.hubble, "energy": energy["total"],
+                     "pressure": energy["pressure"]}
+        dump_outputs(p.dump_outputs, arrays, state, h, decomp)
 
     ms_per_step = elapsed / p.steps * 1e3
     msites = grid_size * p.steps / elapsed / 1e6

@@ -37,14 +37,46 @@ def ext():
                 "pystella_amd._C native extension not built; run "
                 "`python -m pystella_amd.backend.build` (hipcc, gfx950). "
                 f"Underlying error: {e}") from e
-        cache = os.environ.get(
-            "PYSTELLA_JIT_CACHE",
-            os.path.join(os.path.dirname(os.path.dirname(
-                os.path.abspath(__file__))), ".hiprtc_cache"))
-        os.makedirs(cache, exist_ok=True)
-        _C.set_cache_dir(cache)
+        _C.set_cache_dir(_jit_cache_dir())
         _EXT = _C
     return _EXT
+
+
+def _jit_cache_dir():
+    """Directory of the on-disk hiprtc code cache: PYSTELLA_JIT_CACHE
+    if set; else the first of the package tree, the user's cache
+    directory and a per-user directory under the system temp dir that
+    this user can write (the package may be installed or checked out
+    read-only, or belong to another user).  "" (no disk cache, kernels
+    are compiled once per process) if none is writable."""
+    import tempfile
+    cache = os.environ.get("PYSTELLA_JIT_CACHE")
+    if cache:
+        os.makedirs(cache, exist_ok=True)
+        return cache
+    uid = os.getuid()
+    candidates = [
+        os.path.join(os.path.dirname(os.path.dirname(
+            os.path.abspath(__file__))), ".hiprtc_cache"),
+        os.path.join(
+            os.environ.get("XDG_CACHE_HOME")
+            or os.path.join(os.path.expanduser("~"), ".cache"),
+            "pystella_amd", "hiprtc"),
+        os.path.join(tempfile.gettempdir(),
+                     f"pystella_amd-hiprtc-{uid}"),
+    ]
+    for cand in candidates:
+        try:
+            os.makedirs(cand, mode=0o700, exist_ok=True)
+        except OSError:
+            continue
+        if not os.access(cand, os.W_OK | os.X_OK):
+            continue
+        # a predictable name in a shared temp dir: only if it is ours
+        if cand is candidates[-1] and os.stat(cand).st_uid != uid:
+            continue
+        return cand
+    return ""
 
 
 def _stream():

@@ -118,10 +118,9 @@ def test_uneven_split():
     assert (n, s) == (3, 7)
 
 
-def _checkpoint_worker(rank, world_size, mode):
+def _checkpoint_worker(rank, world_size, mode, out_dir):
     import torch
     from pystella_amd.checkpoint import save_checkpoint, load_checkpoint
-    import tempfile
     import os
     h = 1
     grid = (8, 8, 8)
@@ -131,8 +130,9 @@ def _checkpoint_worker(rank, world_size, mode):
     torch.manual_seed(rank)
     f = torch.rand((2,) + pad, dtype=torch.float64)
     decomp.share_halos(f)
-    path = os.path.join(tempfile.gettempdir(),
-                        f"ckpt_test_{mode}_{world_size}.pt")
+    # a per-test directory shared by the ranks: a fixed name in the
+    # system temp dir collides with files left by another user's run
+    path = os.path.join(out_dir, f"ckpt_test_{mode}_{world_size}.pt")
     save_checkpoint(path, decomp, {"f": f}, attrs={"t": 1.5}, mode=mode)
     f2 = torch.zeros_like(f)
     attrs = load_checkpoint(path, decomp, {"f": f2})
@@ -140,12 +140,12 @@ def _checkpoint_worker(rank, world_size, mode):
     assert torch.allclose(f, f2), f"rank {rank} mismatch"
 
 
-def test_checkpoint_gather():
-    run_distributed(_checkpoint_worker, 2, args=("gather",))
+def test_checkpoint_gather(tmp_path):
+    run_distributed(_checkpoint_worker, 2, args=("gather", str(tmp_path)))
 
 
-def test_checkpoint_shard():
-    run_distributed(_checkpoint_worker, 2, args=("shard",))
+def test_checkpoint_shard(tmp_path):
+    run_distributed(_checkpoint_worker, 2, args=("shard", str(tmp_path)))
 
 
 def _overlap_halo_worker(rank, world_size, proc_shape, grid_shape, h):
