@@ -1729,7 +1729,26 @@ class JitLapStage:
         import os as _os
         env = _os.environ.get("PYSTELLA_TILE")
         if env:
-            return tuple(int(x) for x in env.split(","))
+            try:
+                tile = tuple(int(x) for x in env.split(","))
+            except ValueError:
+                tile = ()
+            if len(tile) != 3 or any(t <= 0 for t in tile):
+                raise ValueError(
+                    f"PYSTELLA_TILE={env!r}: expected three positive "
+                    "integers 'TBZ,TBY,XCHUNK'")
+            if (tile[0] * tile[1]) % 64:
+                raise ValueError(
+                    f"PYSTELLA_TILE={env!r}: block of TBZ*TBY = "
+                    f"{tile[0] * tile[1]} threads is not a multiple of "
+                    "the 64-lane wavefront")
+            nthr = tile[0] * tile[1]
+            if nthr & (nthr - 1) or nthr > 1024:
+                # the LDS reduction tree halves the block each level
+                raise ValueError(
+                    f"PYSTELLA_TILE={env!r}: block of TBZ*TBY = {nthr} "
+                    "threads must be a power of two, at most 1024")
+            return tile
         for tile in cls.TILE_CANDIDATES:
             g = _tile_grid(tile, rank_shape)
             if g[0] * g[1] * g[2] >= 2048:
