@@ -50,6 +50,9 @@ class Codegen:
         self.scalars = []           # [(c_name, value_key)]
         self._scalar_index = {}
         self.tmp_names = set(tmp_names)
+        # spelling of the literal one in x**0 and x**-n; kernels that
+        # must not promote a float expression set it to "real(1.0)"
+        self.one = "1.0"
 
     def scalar_param(self, name, idx=()):
         key = (name, tuple(idx)) if idx else name
@@ -121,11 +124,11 @@ class Codegen:
                     isinstance(expr.exponent, numbers.Integral):
                 n = int(expr.exponent)
                 if n == 0:
-                    return "1.0"
+                    return self.one
                 if 1 <= n <= 8:
                     return "ps_pow" + str(n) + f"({base})"
                 if -8 <= n < 0:
-                    return f"(1.0/ps_pow{-n}({base}))"
+                    return f"({self.one}/ps_pow{-n}({base}))"
             return f"pow({base}, {self.emit(expr.exponent)})"
         if isinstance(expr, Call):
             if expr.func == "parity":

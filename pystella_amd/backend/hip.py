@@ -1247,11 +1247,63 @@ def divergence(vec, div, halo=None, dx=None, h=None):
 # HBM traffic per site drops from (f, lap w, f, dfdt, lap r) to
 # (f, dfdt, lap w).
 
-def _lap_stencil_pieces(h, dx, periodic):
+def _real_name(dtype):
+    """C name of the per-site type in the generated ring kernels.  The
+    float64 kernels spell it ``double`` (their source text is pinned:
+    the tuned flagship kernels must not move), every other dtype uses
+    the ``real`` alias that ``geometry_defines`` sets."""
+    if dtype not in _RTYPE:
+        raise TypeError(f"unsupported kernel dtype {dtype}")
+    return "double" if dtype == torch.float64 else "real"
+
+
+def _kernel_ptrs(kern, env):
+    """(pointers, device) of a ring kernel's array arguments, each
+    checked against the kernel's dtype (the device-state scalar buffer
+    is float64 whatever the fields are).  The kernel would read a
+    buffer of another dtype as its own type: garbage, and past the end
+    of a narrower one."""
+    if kern.key is None:
+        raise RuntimeError(
+            f"{type(kern).__name__} was built with compile=False "
+            "(source only) and cannot be launched")
+    for n in kern.ptr_names:
+        want = torch.float64 if n == "state" and kern.state_map \
+            else kern.dtype
+        t = env[n]
+        if isinstance(t, torch.Tensor) and t.dtype != want:
+            raise TypeError(
+                f"argument {n} has dtype {t.dtype}, kernel "
+                f"compiled for {want}")
+    ptrs, dev = [], None
+    for n in kern.ptr_names:
+        t = _check_tensor(n, env[n])
+        dev = t.device
+        ptrs.append(t.data_ptr())
+    return ptrs, dev
+
+
+def _lapc0_define(lapc0, dtype):
+    if dtype == torch.float64:
+        return f"#define LAPC0 ({lapc0!r})\n"
+    return f"#define LAPC0 (real({lapc0!r}))\n"
+
+
+def _lap_stencil_pieces(h, dx, periodic, dtype=torch.float64):
     """Shared codegen for the inline-Laplacian ring kernels: stencil
-    term strings, the center coefficient, and the x-ring load/init
-    forms.  periodic=(px,py,pz) wraps that axis's stencil reads
-    in-kernel (star stencil) so non-decomposed axes need NO halo fill.
+    term strings, the center coefficient, the x-ring load/init forms
+    and the accumulator's initialization.  periodic=(px,py,pz) wraps
+    that axis's stencil reads in-kernel (star stencil) so
+    non-decomposed axes need NO halo fill.
+
+    float64 evaluates ``c0*f0 + sum_s c_s (f[+s] + f[-s])``.  Below
+    float64 the coefficients (16/12, 1/12, ...) are inexact, no longer
+    sum to zero, and the field's mean leaks into the Laplacian (1.3e-6
+    absolute at h=2 for the 0.193 inflaton mean, more than a 1e-6
+    fluctuation's whole signal), so those kernels use the difference
+    form ``sum_s c_s ((f[+s] - f0) + (f[-s] - f0))``: the mean cancels
+    exactly before any coefficient is applied, at two subtractions per
+    neighbour pair in a bandwidth-bound kernel.
     """
     from pystella_amd.derivs import _LAP_COEFS
     inv2 = [1.0 / d / d for d in dx]
@@ -1281,11 +1333,25 @@ def _lap_stencil_pieces(h, dx, periodic):
             zp, zm = f"zpo{s}", f"zmo{s}"
         else:
             zp, zm = f"{s}", f"-{s}"
-        lap_terms.append(
-            f"la += {c!r} * ((ring[fld][H+{s}] + ring[fld][H-{s}])"
-            f"*{inv2[0]!r} + (cp[{yp}] + cp[{ym}])*{inv2[1]!r}"
-            f" + (cp[{zp}] + cp[{zm}])*{inv2[2]!r});")
+        if dtype == torch.float64:
+            lap_terms.append(
+                f"la += {c!r} * ((ring[fld][H+{s}] + ring[fld][H-{s}])"
+                f"*{inv2[0]!r} + (cp[{yp}] + cp[{ym}])*{inv2[1]!r}"
+                f" + (cp[{zp}] + cp[{zm}])*{inv2[2]!r});")
+        else:
+            lap_terms.append(
+                f"la += real({c!r}) * ("
+                f"((ring[fld][H+{s}] - f0) + (ring[fld][H-{s}] - f0))"
+                f"*real({inv2[0]!r})"
+                f" + ((cp[{yp}] - f0) + (cp[{ym}] - f0))"
+                f"*real({inv2[1]!r})"
+                f" + ((cp[{zp}] - f0) + (cp[{zm}] - f0))"
+                f"*real({inv2[2]!r}));")
     lapc0 = coefs[0] * (inv2[0] + inv2[1] + inv2[2])
+    if dtype == torch.float64:
+        la_init = "double la = ring[fld][H] * LAPC0;"
+    else:
+        la_init = "const real f0 = ring[fld][H]; real la = real(0.0);"
     if px_:
         x_off = ("int xq = i + 2 * H; "
                  "if (xq >= NX + H) xq -= NX;")
@@ -1298,7 +1364,8 @@ def _lap_stencil_pieces(h, dx, periodic):
         x_off = ""
         ring_load = "ring[fld][2 * H] = fp[(long)(i + 2 * H) * sx];"
         ring_init = "ring[fld][p] = fp[(long)(i0 + p) * sx];"
-    return wrap_decls, lap_terms, lapc0, x_off, ring_load, ring_init
+    return (wrap_decls, lap_terms, lapc0, x_off, ring_load, ring_init,
+            la_init)
 
 
 
@@ -1317,24 +1384,24 @@ extern "C" __global__ __launch_bounds__(TBZ * TBY) void {name}(
     const int i1 = (i0 + XCHUNK < NX) ? i0 + XCHUNK : NX;
     if (k < NZ && j < NY) {{
         const long sx = PSY * PSZ;
-        double ring[NF][2 * H + 1];
+        {R} ring[NF][2 * H + 1];
         #pragma unroll
         for (int fld = 0; fld < NF; ++fld) {{
-            const double* fp = {fname} + (long)fld * PVOL
+            const {R}* fp = {fname} + (long)fld * PVOL
                                + (long)(j + H) * PSZ + (k + H);
             #pragma unroll
             for (int p = 0; p < 2 * H; ++p)
                 ring[fld][p] = fp[(long)(i0 + p) * sx];
         }}
         for (int i = i0; i < i1; ++i) {{
-            double lapv[NF];
+            {R} lapv[NF];
             #pragma unroll
             for (int fld = 0; fld < NF; ++fld) {{
-                const double* fp = {fname} + (long)fld * PVOL
+                const {R}* fp = {fname} + (long)fld * PVOL
                                    + (long)(j + H) * PSZ + (k + H);
                 ring[fld][2 * H] = fp[(long)(i + 2 * H) * sx];
-                const double* cp = fp + (long)(i + H) * sx;
-                double la = ring[fld][H] * LAPC0;
+                const {R}* cp = fp + (long)(i + H) * sx;
+                {la_init}
                 {lap_terms}
                 lapv[fld] = la;
 #if STORE_LAP
@@ -1361,6 +1428,21 @@ class _LapCodegen(Codegen):
         super().__init__(field_args, halo, rank_shape)
         self.f_name = f_name
         self.lap_name = lap_name
+        # set while a reducer's per-site value is emitted in a kernel
+        # whose real is narrower than double: run-time scalars enter
+        # there as the doubles they are passed as.  Narrowed, the scale
+        # factor would be off by up to 6e-8, the same at every site, so
+        # the kinetic and gradient energies that feed the float64
+        # Friedmann ODE would carry twice that instead of averaging
+        # their rounding away.  The field part of the value is still
+        # evaluated in real and widens where the scalar meets it.
+        self.wide_scalars = False
+
+    def scalar_param(self, name, idx=()):
+        v = super().scalar_param(name, idx)
+        if self.wide_scalars and v.startswith("real(s_"):
+            return v[len("real("):-1]
+        return v
 
     def field_access(self, f, outer_idx):
         if f.is_spatial and not any(f.shift) and len(outer_idx) <= 1:
@@ -1378,21 +1460,29 @@ class JitLapReduction:
     def __init__(self, entries, field_args, scalar_names, halo, rank_shape,
                  dx, nf, f_name="f", lap_name="lap_f", name="lapred_map",
                  tile=(64, 4, 64), store_lap=True,
-                 periodic=(False, False, False)):
+                 periodic=(False, False, False), dtype=torch.float64,
+                 compile=True):
         from pystella_amd.derivs import _LAP_COEFS
         self.rank_shape = tuple(rank_shape)
         self.tile = tile
+        self.dtype = dtype
+        self.state_map = None
+        R = _real_name(dtype)
         self.store_lap = store_lap
         self.entries = entries
         h = max(halo) if isinstance(halo, (tuple, list)) else halo
         self.nf = nf
         cg = _LapCodegen(field_args, halo, rank_shape, f_name, lap_name)
+        if R == "real":
+            cg.one = "real(1.0)"
 
         init_lines, body_lines, combine_cases = [], [], []
         for r, (expr, op) in enumerate(entries):
             init_lines.append(f"acc[{r}] = {_OP_INIT[op]};")
             comb = _OP_COMBINE[op]
+            cg.wide_scalars = R == "real"
             val = cg.emit(expr)
+            cg.wide_scalars = False
             body_lines.append(
                 "{ const double a = acc[%d]; const double b = %s; "
                 "acc[%d] = %s; }" % (r, val, r, comb))
@@ -1402,7 +1492,7 @@ class JitLapReduction:
         # Laplacian stencil terms with dx baked in
         self.periodic = tuple(periodic)
         (wrap_decls, lap_terms, lapc0, x_off, ring_load,
-         ring_init) = _lap_stencil_pieces(h, dx, periodic)
+         ring_init, la_init) = _lap_stencil_pieces(h, dx, periodic, dtype)
 
         # pointer params: stencil field first, then lap (if stored),
         # then the rest
@@ -1413,25 +1503,27 @@ class JitLapReduction:
         by_name = {fa.name: fa for fa in field_args}
         self.field_args = [by_name[n] for n in self.ptr_names if n in by_name]
         ptr_params = ", ".join(
-            f"double* __restrict__ {n}" for n in self.ptr_names)
+            f"{R}* __restrict__ {n}" for n in self.ptr_names)
         dbl_params = ", ".join(f"double {c}" for c, _ in cg.scalars)
         params = ", ".join(x for x in (
             ptr_params, "double* __restrict__ partials", dbl_params) if x)
 
-        defines = geometry_defines(halo, rank_shape)
+        defines = geometry_defines(halo, rank_shape, rtype=_RTYPE[dtype])
         defines += _tile_defines(tile, rank_shape)
         defines += f"#define COMBINE(r, a, b) ({combine})\n"
-        defines += f"#define LAPC0 ({lapc0!r})\n"
+        defines += _lapc0_define(lapc0, dtype)
         defines += f"#define STORE_LAP {1 if store_lap else 0}\n"
         src = LAPRED_TEMPLATE.format(
             defines=defines, preamble=PREAMBLE, nred=len(entries), nf=nf,
             name=name, params=params, fname=f_name, lapname=lap_name,
+            R=R, la_init=la_init,
             init="\n    ".join(init_lines),
             lap_terms="\n                ".join(lap_terms),
             body="\n            ".join(body_lines))
         self.source = src
         self.scalar_keys = [k for _, k in cg.scalars]
-        self.key = ext().jit_compile(src, name)
+        # compile=False: source only (inspectable without a device)
+        self.key = ext().jit_compile(src, name) if compile else None
         self.grid = _tile_grid(tile, rank_shape)
         self.block = tile[0] * tile[1]
         self.nblk = self.grid[0] * self.grid[1] * self.grid[2]
@@ -1440,12 +1532,7 @@ class JitLapReduction:
     _finish = JitReduction._finish
 
     def __call__(self, env):
-        dev = None
-        ptrs = []
-        for n in self.ptr_names:
-            t = _check_tensor(n, env[n])
-            dev = t.device
-            ptrs.append(t.data_ptr())
+        ptrs, dev = _kernel_ptrs(self, env)
         nred = len(self.entries)
         if (self._partials is None
                 or self._partials.device != dev
@@ -1497,10 +1584,10 @@ extern "C" __global__ __launch_bounds__(TBZ * TBY, MINW) void {name}(
     if (k < k1b && j < j1b) {{
         const long sx = PSY * PSZ;
         {wrap_decls}
-        double ring[NF][2 * H + 1];
+        {R} ring[NF][2 * H + 1];
         #pragma unroll
         for (int fld = 0; fld < NF; ++fld) {{
-            const double* fp = {fname} + (long)fld * PVOL
+            const {R}* fp = {fname} + (long)fld * PVOL
                                + (long)(j + H) * PSZ + (k + H);
             #pragma unroll
             for (int p = 0; p < 2 * H; ++p) {{
@@ -1508,15 +1595,15 @@ extern "C" __global__ __launch_bounds__(TBZ * TBY, MINW) void {name}(
             }}
         }}
         for (int i = i0; i < i1; ++i) {{
-            double lapv[NF];
+            {R} lapv[NF];
             {x_off}
             #pragma unroll
             for (int fld = 0; fld < NF; ++fld) {{
-                const double* fp = {fname} + (long)fld * PVOL
+                const {R}* fp = {fname} + (long)fld * PVOL
                                    + (long)(j + H) * PSZ + (k + H);
                 {ring_load}
-                const double* cp = fp + (long)(i + H) * sx;
-                double la = ring[fld][H] * LAPC0;
+                const {R}* cp = fp + (long)(i + H) * sx;
+                {la_init}
                 {lap_terms}
                 lapv[fld] = la;
             }}
@@ -1548,7 +1635,7 @@ class _NTLapCodegen(_LapCodegen):
         # state scalars are hoisted into per-thread registers once at
         # kernel entry (st_<name>, see JitLapStage state prologue)
         if name in self.state_map and not idx:
-            return f"st_{name}"
+            return f"std_{name}" if self.wide_scalars else f"st_{name}"
         return super().scalar_param(name, idx)
 
     def field_access(self, f, outer_idx):
@@ -1606,11 +1693,11 @@ extern "C" __global__ __launch_bounds__(TBZ * TBY, MINW) void {name}(
     if (k < sh_k1[box] && j < sh_j1[box]) {{
         const long sx = PSY * PSZ;
         {wrap_decls}
-        double lapv[NF];
-        double ring[NF][2 * H + 1];
+        {R} lapv[NF];
+        {R} ring[NF][2 * H + 1];
         #pragma unroll
         for (int fld = 0; fld < NF; ++fld) {{
-            const double* fp = {fname} + (long)fld * PVOL
+            const {R}* fp = {fname} + (long)fld * PVOL
                                + (long)(j + H) * PSZ + (k + H);
             #pragma unroll
             for (int p = 0; p < 2 * H; ++p) {{
@@ -1621,11 +1708,11 @@ extern "C" __global__ __launch_bounds__(TBZ * TBY, MINW) void {name}(
             {x_off}
             #pragma unroll
             for (int fld = 0; fld < NF; ++fld) {{
-                const double* fp = {fname} + (long)fld * PVOL
+                const {R}* fp = {fname} + (long)fld * PVOL
                                    + (long)(j + H) * PSZ + (k + H);
                 {ring_load}
-                const double* cp = fp + (long)(i + H) * sx;
-                double la = ring[fld][H] * LAPC0;
+                const {R}* cp = fp + (long)(i + H) * sx;
+                {la_init}
                 {lap_terms}
                 lapv[fld] = la;
             }}
@@ -1672,10 +1759,10 @@ extern "C" __global__ __launch_bounds__(TBZ * TBY, MINW) void {name}(
     if (k < k1b && j < j1b) {{
         const long sx = PSY * PSZ;
         {wrap_decls}
-        double ring[NF][2 * H + 1];
+        {R} ring[NF][2 * H + 1];
         #pragma unroll
         for (int fld = 0; fld < NF; ++fld) {{
-            const double* fp = {fname} + (long)fld * PVOL
+            const {R}* fp = {fname} + (long)fld * PVOL
                                + (long)(j + H) * PSZ + (k + H);
             #pragma unroll
             for (int p = 0; p < 2 * H; ++p) {{
@@ -1761,7 +1848,8 @@ class JitLapStage:
                  lap_name="lap_f", name="rk_lapstage", tile=None,
                  nt=True, state_map=None, min_waves=1,
                  periodic=(False, False, False), section_size=None,
-                 guard_stores=frozenset(), guard_scalar=None):
+                 guard_stores=frozenset(), guard_scalar=None,
+                 dtype=torch.float64, compile=True):
         import os as _os
         from pystella_amd.field import (
             Field, Subscript, Variable, is_number, iter_exprs, walk_expr)
@@ -1772,12 +1860,18 @@ class JitLapStage:
         # changes (occupancy throttling for cache-thrash regimes)
         self.shmem = 0
         self.tile = tile
+        self.dtype = dtype
+        # per-site type: arrays, ring, Laplacian, RHS and the 2N update;
+        # acc[], the LDS tree, partials and the state buffer stay double
+        R = _real_name(dtype)
         self.entries = entries
         h = max(halo) if isinstance(halo, (tuple, list)) else halo
         self.nf = nf
         self.state_map = state_map
         cg = _NTLapCodegen(field_args, halo, rank_shape, f_name, lap_name,
                            state_map=state_map)
+        if R == "real":
+            cg.one = "real(1.0)"
 
         tmp_items = list((tmp_instructions or {}).items())
         store_items = list(map_dict.items())
@@ -1837,18 +1931,18 @@ class JitLapStage:
             off = "(((long)i*NY + j)*NZ + k)"
             if lin:
                 off = f"({lin}L*UVOL + {off})"
-            return (f"const double pl_{nm}_{lin} = "
+            return (f"const {R} pl_{nm}_{lin} = "
                     f"__builtin_nontemporal_load(&{nm}[{off}]);")
 
         # ---- shared emission helpers -----------------------------------
         self.periodic = tuple(periodic)
         (wrap_decls, lap_terms, lapc0, x_off, ring_load,
-         ring_init) = _lap_stencil_pieces(h, dx, periodic)
+         ring_init, la_init) = _lap_stencil_pieces(h, dx, periodic, dtype)
 
         def _emit_tmps(items, out):
             for lhs, rhs in items:
                 tname = lhs.name if hasattr(lhs, "name") else str(lhs)
-                out.append(f"const double {tname} = {cg.emit(rhs)};")
+                out.append(f"const {R} {tname} = {cg.emit(rhs)};")
 
         def _emit_stores(items, out):
             for lhs, rhs in items:
@@ -1863,17 +1957,17 @@ class JitLapStage:
                     out.append(f"{dst} = {val};")
 
         def _fp_decl(lin):
-            return (f"    const double* fp = {f_name} + (long)fld * PVOL"
+            return (f"    const {R}* fp = {f_name} + (long)fld * PVOL"
                     f" + (long)(j + H) * PSZ + (k + H);")
 
         def _stencil_block(lin, out):
-            out.append(f"double lapv_{lin};")
+            out.append(f"{R} lapv_{lin};")
             out.append("{")
             out.append(f"    const int fld = {lin};")
             out.append(_fp_decl(lin))
             out.append("    " + ring_load)
-            out.append("    const double* cp = fp + (long)(i + H) * sx;")
-            out.append("    double la = ring[fld][H] * LAPC0;")
+            out.append(f"    const {R}* cp = fp + (long)(i + H) * sx;")
+            out.append("    " + la_init)
             for t in lap_terms:
                 out.append("    " + t)
             out.append(f"    lapv_{lin} = la;")
@@ -1888,7 +1982,17 @@ class JitLapStage:
 
         init_lines, combine_cases = [], []
         for nm, sidx in sorted((state_map or {}).items()):
-            init_lines.append(f"const double st_{nm} = state[{sidx}];")
+            if R == "double":
+                init_lines.append(
+                    f"const double st_{nm} = state[{sidx}];")
+            else:
+                # narrowed once at kernel entry, so the per-site
+                # expressions that use it stay in real; the reducers
+                # take the double (see _LapCodegen.wide_scalars)
+                init_lines.append(
+                    f"const double std_{nm} = state[{sidx}];")
+                init_lines.append(
+                    f"const real st_{nm} = real(std_{nm});")
         for r, (expr, op) in enumerate(entries):
             init_lines.append(f"acc[{r}] = {_OP_INIT[op]};")
             combine_cases.append(f"(r == {r}) ? {_OP_COMBINE[op]} : ")
@@ -1896,7 +2000,9 @@ class JitLapStage:
 
         def _entry_lines(out):
             for r, (expr, op) in enumerate(entries):
+                cg.wide_scalars = R == "real"
                 val = cg.emit(expr)
+                cg.wide_scalars = False
                 out.append(
                     "{ const double a = acc[%d]; const double b = %s; "
                     "acc[%d] = %s; }" % (r, val, r, _OP_COMBINE[op]))
@@ -2061,7 +2167,8 @@ class JitLapStage:
                 _emit_stores(normal, lines)
                 if guarded:
                     cond = cg.scalar_param(guard_scalar)
-                    lines.append(f"if ({cond} != 0.0) {{")
+                    zero = "0.0" if R == "double" else "real(0.0)"
+                    lines.append(f"if ({cond} != {zero}) {{")
                     _emit_stores(guarded, lines)
                     lines.append("}")
             else:
@@ -2078,7 +2185,7 @@ class JitLapStage:
         self.field_args = [by_name[n] for n in self.ptr_names
                            if n in by_name]
         ptr_params = ", ".join(
-            f"double* __restrict__ {n}" for n in self.ptr_names)
+            f"{R}* __restrict__ {n}" for n in self.ptr_names)
         if state_map:
             self.ptr_names.append("state")
             ptr_params += ", const double* __restrict__ state"
@@ -2090,18 +2197,18 @@ class JitLapStage:
             ptr_params, "double* __restrict__ partials", int_params,
             dbl_params) if x)
 
-        defines = geometry_defines(halo, rank_shape)
+        defines = geometry_defines(halo, rank_shape, rtype=_RTYPE[dtype])
         defines += _tile_defines(tile, rank_shape)
         defines += f"#define MINW {min_waves}\n"
         defines += f"#define COMBINE(r, a, b) ({combine})\n"
-        defines += f"#define LAPC0 ({lapc0!r})\n"
+        defines += _lapc0_define(lapc0, dtype)
         if sectioned:
             src = LAPSTAGE_SEC_TEMPLATE.format(
                 defines=defines, preamble=PREAMBLE, nred=len(entries),
                 nf=nf, name=name, params=params, fname=f_name,
                 init="\n    ".join(init_lines),
                 wrap_decls="\n        ".join(wrap_decls),
-                x_off=x_off, ring_init=ring_init,
+                x_off=x_off, ring_init=ring_init, R=R,
                 site_body="\n            ".join(lines))
             self._shell_parts = None
         else:
@@ -2111,6 +2218,7 @@ class JitLapStage:
                 init="\n    ".join(init_lines),
                 wrap_decls="\n        ".join(wrap_decls),
                 x_off=x_off, ring_load=ring_load, ring_init=ring_init,
+                R=R, la_init=la_init,
                 lap_terms="\n                ".join(lap_terms),
                 body="\n            ".join(lines))
             src = LAPSTAGE_TEMPLATE.format(**fmt)
@@ -2118,7 +2226,10 @@ class JitLapStage:
         self._shell_cache = {}
         self.source = src
         self.scalar_keys = [k for _, k in cg.scalars]
-        self.key = ext().jit_compile(src, name)
+        # compile=False: source only (``.source``, ``shell_source``),
+        # inspectable without a device; such a kernel cannot be launched
+        self._compile = compile
+        self.key = ext().jit_compile(src, name) if compile else None
         self.grid = _tile_grid(tile, rank_shape)
         self.block = tile[0] * tile[1]
         self.nblk = self.grid[0] * self.grid[1] * self.grid[2]
@@ -2141,10 +2252,24 @@ class JitLapStage:
         return grid[0] * grid[1] * grid[2]
 
     # -- multi-box shell launch (all boundary slabs in ONE kernel) ------
+    def shell_source(self, boxes):
+        """HIP source of the shell form over ``boxes`` (no device)."""
+        return self._shell_build(tuple(boxes))[0]
+
     def _get_shell(self, boxes):
         cached = self._shell_cache.get(boxes)
         if cached is not None:
             return cached
+        src, name, total = self._shell_build(boxes)
+        if not self._compile:
+            raise RuntimeError(
+                "JitLapStage was built with compile=False (source "
+                "only) and cannot be launched")
+        cached = (ext().jit_compile(src, name), total)
+        self._shell_cache[boxes] = cached
+        return cached
+
+    def _shell_build(self, boxes):
         if self._shell_parts is None:
             raise RuntimeError("shell form unavailable (sectioned)")
         grids = [self._box_geometry(b)[0] for b in boxes]
@@ -2165,10 +2290,7 @@ class JitLapStage:
             i0s=ints(b[0] for b in boxes), i1s=ints(b[1] for b in boxes),
             gzs=ints(g[0] for g in grids), gys=ints(g[1] for g in grids),
             blk0s=ints(blk0), **fmt)
-        kid = ext().jit_compile(src, fmt["name"])
-        cached = (kid, sum(nbs))
-        self._shell_cache[boxes] = cached
-        return cached
+        return src, fmt["name"], sum(nbs)
 
     def shell_nblk(self, boxes):
         return self._get_shell(tuple(boxes))[1]
@@ -2176,11 +2298,8 @@ class JitLapStage:
     def launch_shell(self, env, boxes, partials, bid0, nblk_tot):
         """ONE launch covering every box in ``boxes`` (the rank's
         boundary slabs); per-block partials land flat at ``bid0``."""
+        ptrs, _ = _kernel_ptrs(self, env)
         kid, total = self._get_shell(tuple(boxes))
-        ptrs = []
-        for n in self.ptr_names:
-            t = _check_tensor(n, env[n])
-            ptrs.append(t.data_ptr())
         doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
         ext().jit_launch(kid, total, 1, 1, self.block, 1, 1,
                          self.shmem, _stream(),
@@ -2191,10 +2310,7 @@ class JitLapStage:
         """Launch over a sub-box, writing this launch's per-block
         partials at column offset ``bid0`` of the shared ``partials``
         buffer [nred, nblk_tot].  Stream-ordered, no host sync."""
-        ptrs = []
-        for n in self.ptr_names:
-            t = _check_tensor(n, env[n])
-            ptrs.append(t.data_ptr())
+        ptrs, _ = _kernel_ptrs(self, env)
         grid, ints = self._box_geometry(box)
         doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
         ext().jit_launch(self.key, grid[0], grid[1], grid[2],
@@ -2206,9 +2322,7 @@ class JitLapStage:
         """Full-grid launch without finishing the reduction; returns the
         raw per-block partials tensor [nred, nblk] (stream-ordered, no
         host synchronization)."""
-        dev = None
-        for n in self.ptr_names:
-            dev = _check_tensor(n, env[n]).device
+        _, dev = _kernel_ptrs(self, env)
         nred = len(self.entries)
         if (self._partials is None
                 or self._partials.device != dev
@@ -2221,9 +2335,7 @@ class JitLapStage:
         return self._partials
 
     def __call__(self, env):
-        dev = None
-        for n in self.ptr_names:
-            dev = _check_tensor(n, env[n]).device
+        _, dev = _kernel_ptrs(self, env)
         self.launch_only(env)
         return self._finish(dev)
 
@@ -2325,19 +2437,23 @@ def get_lap_stage_kernel(map_dict, tmp_instructions, entries, field_args,
                          f_name="f", lap_name="lap_f",
                          name="rk_lapstage", tile=None, nt=True,
                          state_map=None, periodic=(False, False, False),
-                         guard_stores=frozenset(), guard_scalar=None):
+                         guard_stores=frozenset(), guard_scalar=None,
+                         dtype=torch.float64, compile=True):
     return JitLapStage(map_dict, tmp_instructions, entries, field_args,
                        scalar_names, halo, rank_shape, dx, nf,
                        f_name=f_name, lap_name=lap_name, name=name,
                        tile=tile, nt=nt, state_map=state_map,
                        periodic=periodic, guard_stores=guard_stores,
-                       guard_scalar=guard_scalar)
+                       guard_scalar=guard_scalar, dtype=dtype,
+                       compile=compile)
 
 
 def get_lap_reduction_kernel(entries, field_args, scalar_names, halo,
                              rank_shape, dx, nf, f_name="f",
                              lap_name="lap_f", tile=(64, 4, 64),
-                             store_lap=True):
+                             store_lap=True, dtype=torch.float64,
+                             compile=True):
     return JitLapReduction(entries, field_args, scalar_names, halo,
                            rank_shape, dx, nf, f_name, lap_name, tile=tile,
-                           store_lap=store_lap)
+                           store_lap=store_lap, dtype=dtype,
+                           compile=compile)

@@ -27,6 +27,30 @@ __all__ = ["FusedLaplacianReduction", "StencilRKStepper",
            "DeviceFriedmannLoop"]
 
 
+def _field_dtype(env, field_args):
+    """The one dtype shared by the spatial field arrays of a fused
+    kernel call (the kernels are generated for a single ``real``
+    type); mixed dtypes raise TypeError."""
+    seen = {fa.name: env[fa.name].dtype for fa in field_args
+            if fa.spatial and isinstance(env.get(fa.name), torch.Tensor)}
+    if len(set(seen.values())) > 1:
+        raise TypeError(
+            "the field arrays of one fused kernel call must share one "
+            "dtype, got " + ", ".join(
+                f"{n}: {d}" for n, d in sorted(seen.items())))
+    dtype = next(iter(seen.values()), None)
+    return torch.float64 if dtype is None else dtype
+
+
+def _widened(env):
+    """``env`` with every floating tensor as float64 (float64 tensors
+    are passed through as they are).  The CPU oracles evaluate the
+    reducers on this: like the kernels they sum in float64 and take
+    the scale factor as a double, whatever the fields' dtype."""
+    return {k: v.double() if isinstance(v, torch.Tensor)
+            and v.is_floating_point() else v for k, v in env.items()}
+
+
 class FusedLaplacianReduction(Reduction):
     """Computes ``lap_f = ∇² f`` (all outer components) *and* the given
     reductions — whose expressions may reference both ``f`` and the
@@ -68,20 +92,33 @@ class FusedLaplacianReduction(Reduction):
             from itertools import product
             for s in product(*[range(n) for n in f.shape[:-3]]):
                 self.derivs._apply_lap_cpu(f[s], lap[s])
-            return super().__call__(**kwargs)
+            return super().__call__(**_widened(kwargs))
 
         rank_shape = self._infer_shapes(kwargs)
+        dtype = _field_dtype(
+            kwargs, [fa for fa in self.field_args
+                     if self.store_lap or fa.name != self.lap_name])
         if self._fused_kernel is None or \
-                self._fused_kernel.rank_shape != rank_shape:
-            from pystella_amd.backend.hip import get_lap_reduction_kernel
+                self._fused_kernel.rank_shape != rank_shape or \
+                self._fused_kernel.dtype != dtype:
             nf = int(np.prod(f.shape[:-3])) if f.dim() > 3 else 1
-            self._fused_kernel = get_lap_reduction_kernel(
-                [(expr, op) for _, _, expr, op in self.flat],
-                self.field_args, sorted(self.scalar_names),
-                self.halo_shape, rank_shape, self.derivs.dx, nf,
-                self.f_name, self.lap_name, store_lap=self.store_lap)
+            self._fused_kernel = self.lap_reduction_kernel(
+                rank_shape, nf, dtype)
         local = self._fused_kernel(kwargs)
         return self._combine(local, rank_shape)
+
+    def lap_reduction_kernel(self, rank_shape, nf, dtype=torch.float64,
+                             compile=True):
+        """The fused kernel (``backend.hip.JitLapReduction``) for
+        ``nf`` stencil components of ``dtype``; with ``compile=False``
+        it carries its HIP source only and no device is needed."""
+        from pystella_amd.backend.hip import get_lap_reduction_kernel
+        return get_lap_reduction_kernel(
+            [(expr, op) for _, _, expr, op in self.flat],
+            self.field_args, sorted(self.scalar_names),
+            self.halo_shape, rank_shape, self.derivs.dx, nf,
+            self.f_name, self.lap_name, store_lap=self.store_lap,
+            dtype=dtype, compile=compile)
 
 
 class _StageRedMap:
@@ -137,6 +174,39 @@ class _StageRedMap:
         self._map.scalar_names = scal
         self._hip_kernel = None
         self._kernel_shape = None
+        self._kernel_dtype = None
+
+    def _env_dtype(self, env):
+        """dtype of the stage's field arrays (mixed: TypeError).  The
+        ring kernels take the padded field, its companions and the k
+        arrays; the Laplacian array never exists."""
+        if self.ring is not None:
+            laps = {f"lap_{r[3]}" for r in self.ring}
+            fargs = [fa for fargs in self._ring_field_args
+                     for fa in fargs if fa.name not in laps]
+        else:
+            fargs = self._map.field_args
+        return _field_dtype(env, fargs)
+
+    def ring_kernels(self, rank_shape, dtype=torch.float64, suffix="",
+                     **kwargs):
+        """One register-ring stage kernel per stencil family for
+        ``rank_shape`` and ``dtype``; ``kwargs`` (state_map, periodic,
+        tile, compile) go to ``backend.hip.JitLapStage``.  With
+        ``compile=False`` the kernels carry their HIP source only and
+        no device is needed."""
+        from pystella_amd.backend.hip import get_lap_stage_kernel
+        m = self._map
+        return [
+            get_lap_stage_kernel(
+                rk_o, tmp_o, red_o or [(0.0, "sum")], fargs, [],
+                m.halo_shape, rank_shape, self.derivs.dx, nf,
+                f_name=f_name, lap_name=f"lap_{f_name}",
+                name=f"{m.name}_{f_name}{suffix}",
+                guard_stores=self.guard_kstores,
+                guard_scalar="store_k", dtype=dtype, **kwargs)
+            for (rk_o, tmp_o, red_o, f_name, nf), fargs
+            in zip(self.ring, self._ring_field_args)]
 
     def __call__(self, queue=None, **kwargs):
         import torch as _torch
@@ -146,24 +216,15 @@ class _StageRedMap:
         on_gpu = any(isinstance(v, _torch.Tensor) and v.is_cuda
                      for v in env.values())
         if on_gpu:
+            dtype = self._env_dtype(env)
             if self._hip_kernel is None or \
-                    self._kernel_shape != rank_shape:
+                    self._kernel_shape != rank_shape or \
+                    self._kernel_dtype != dtype:
                 self._kernel_shape = rank_shape
+                self._kernel_dtype = dtype
                 if self.ring is not None:
-                    from pystella_amd.backend.hip import (
-                        get_lap_stage_kernel)
-                    self._hip_kernel = [
-                        get_lap_stage_kernel(
-                            rk_o, tmp_o,
-                            red_o or [(0.0, "sum")],
-                            fargs, [], m.halo_shape, rank_shape,
-                            self.derivs.dx, nf, f_name=f_name,
-                            lap_name=f"lap_{f_name}",
-                            name=f"{m.name}_{f_name}",
-                            guard_stores=self.guard_kstores,
-                            guard_scalar="store_k")
-                        for (rk_o, tmp_o, red_o, f_name, nf), fargs
-                        in zip(self.ring, self._ring_field_args)]
+                    self._hip_kernel = self.ring_kernels(
+                        rank_shape, dtype)
                 else:
                     from pystella_amd.backend.hip import (
                         get_stage_reduction_kernel)
@@ -195,7 +256,8 @@ class _StageRedMap:
                 for s in product(*[range(n) for n in f.shape[:-3]]):
                     self.derivs._apply_lap_cpu(f[s], lap[s])
                 env2[lap_name] = lap
-            local = self.reduction._local_torch(env2, rank_shape)
+            local = self.reduction._local_torch(_widened(env2),
+                                                rank_shape)
         from pystella_amd.backend.torcheval import (
             EvalContext, eval_statements)
         ctx = EvalContext(m.halo_shape, rank_shape)
@@ -589,6 +651,8 @@ class DeviceFriedmannLoop:
     """
 
     STATE_LEN = 8
+    # state-buffer slots the stage kernels read (see JitFriedmann)
+    STATE_MAP = {"a": 0, "hubble": 4}
 
     def __init__(self, stepper, decomp, expand, grid_size, dt,
                  mpl=1.0):
@@ -995,30 +1059,24 @@ class DeviceFriedmannLoop:
         m = smap._map
         rank_shape = m._infer_rank_shape(env)
         kerns = smap._hip_kernel
+        dtype = smap._env_dtype(env)
         ok = (isinstance(kerns, list) and kerns
               and getattr(kerns[0], "state_map", None) is not None
-              and kerns[0].rank_shape == rank_shape)
+              and kerns[0].rank_shape == rank_shape
+              and kerns[0].dtype == dtype)
         if not ok:
-            from pystella_amd.backend.hip import get_lap_stage_kernel
             periodic = self._periodic_axes(smap, rank_shape)
 
             def build(tile=None, suffix=""):
-                return [
-                    get_lap_stage_kernel(
-                        rk_o, tmp_o, red_o or [(0.0, "sum")], fargs, [],
-                        m.halo_shape, rank_shape, smap.derivs.dx, nf,
-                        f_name=f_name, lap_name=f"lap_{f_name}",
-                        name=f"{m.name}_{f_name}{suffix}",
-                        state_map={"a": 0, "hubble": 4},
-                        periodic=periodic, tile=tile,
-                        guard_stores=smap.guard_kstores,
-                        guard_scalar="store_k")
-                    for (rk_o, tmp_o, red_o, f_name, nf), fargs
-                    in zip(smap.ring, smap._ring_field_args)]
+                return smap.ring_kernels(
+                    rank_shape, dtype, suffix=suffix,
+                    state_map=self.STATE_MAP, periodic=periodic,
+                    tile=tile)
 
             kerns = build()
             smap._hip_kernel = kerns
             smap._kernel_shape = rank_shape
+            smap._kernel_dtype = dtype
             smap._ring_builder = build
             smap._slab_variants = {}
         has_red = [bool(r[2]) for r in smap.ring]
