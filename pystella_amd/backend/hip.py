@@ -1145,6 +1145,225 @@ def projector_op(op, kshape, ptrs, eff, times_abs_k=False):
 
 
 # ---------------------------------------------------------------------------
+# fused k-space kernels of SpectralCollocator and SpectralPoissonSolver:
+# one launch per operation, fk read once, no k-space temporaries
+# (reference pystella/fourier/derivs.py:93-108 and poisson.py:96-101
+# run each as ONE generated kernel; these close K13 and K14).  Complex
+# values move as one 16-byte access per mode.  Every product that is
+# then added goes through rounded(): the JIT compiles with
+# -ffp-contract=fast, which fuses even under a contract(off) pragma, and
+# a fused multiply-add is not the torch chain's result.  The empty asm
+# emits nothing; it only hides the product from the contraction.
+
+KSPACE_KERNEL = """
+__device__ inline double rounded(double x)
+{{ asm("" : "+v"(x)); return x; }}
+
+extern "C" __global__ __launch_bounds__(256) void {name}(
+    {params})
+{{
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= VOLK) return;
+    const int kk = (int)(idx % NKZ);
+    const int jj = (int)((idx / NKZ) % NKY);
+    const int ii = (int)(idx / ((long)NKZ * NKY));
+    (void)ii; (void)jj; (void)kk;
+    {body}
+}}
+"""
+
+KSPACE_DERIV_OUTS = ("pdx", "pdy", "pdz", "lap")
+
+
+def _kspace_derivs_pieces(outs):
+    params = ["const double2* __restrict__ fk"]
+    params += [f"double2* __restrict__ {o}" for o in outs]
+    tables = [f"k1{'xyz'[mu]}" for mu in range(3) if f"pd{'xyz'[mu]}" in outs]
+    if "lap" in outs:
+        tables += ["k2x", "k2y", "k2z"]
+    params += [f"const double* __restrict__ {t}" for t in tables]
+    params.append("const double inv_n")
+    body = ["const double2 v = fk[idx];",
+            "const double2 t = make_double2(v.x * inv_n, v.y * inv_n);"]
+    for mu, (ax, i) in enumerate(zip("xyz", ("ii", "jj", "kk"))):
+        if f"pd{ax}" in outs:
+            body += [f"const double q{ax} = k1{ax}[{i}];",
+                     f"pd{ax}[idx] = make_double2(-q{ax} * t.y, "
+                     f"q{ax} * t.x);"]
+    if "lap" in outs:
+        body += ["const double kx = k2x[ii], ky = k2y[jj], kz = k2z[kk];",
+                 "const double mk2 = -((rounded(kx * kx) + rounded(ky * ky))",
+                 "                     + rounded(kz * kz));",
+                 "lap[idx] = make_double2(mk2 * t.x, mk2 * t.y);"]
+    return params, body
+
+
+def _kspace_pieces(op, flags):
+    """(parameter list, body lines) of kernel ``op``; consumes ``flags``."""
+    if op == "derivs":
+        outs = flags.pop("outs", None)
+        if not outs or set(outs) - set(KSPACE_DERIV_OUTS):
+            raise ValueError(
+                f"outs must be a non-empty subset of {KSPACE_DERIV_OUTS}, "
+                f"got {outs!r}")
+        outs = tuple(o for o in KSPACE_DERIV_OUTS if o in outs)
+        params, body = _kspace_derivs_pieces(outs)
+    elif op == "div_accum":
+        mu = int(flags.pop("mu"))
+        accumulate = bool(flags.pop("accumulate"))
+        if mu not in (0, 1, 2):
+            raise ValueError(f"mu must be 0, 1 or 2, got {mu}")
+        params = ["const double2* __restrict__ fk",
+                  "double2* __restrict__ div_k",
+                  "const double* __restrict__ k1", "const double inv_n"]
+        body = ["const double2 v = fk[idx];",
+                f"const double q = k1[{('ii', 'jj', 'kk')[mu]}];",
+                "double2 term = make_double2((-q * v.y) * inv_n, "
+                "(q * v.x) * inv_n);"]
+        if accumulate:
+            body += ["const double2 d = div_k[idx];",
+                     "term = make_double2(d.x + rounded(term.x), "
+                     "d.y + rounded(term.y));"]
+        body.append("div_k[idx] = term;")
+    elif op == "poisson":
+        # sol may be rhok itself: no __restrict__ on either
+        params = ["const double2* rhok", "double2* sol",
+                  "const double* __restrict__ ex",
+                  "const double* __restrict__ ey",
+                  "const double* __restrict__ ez",
+                  "const double inv_n", "const double m_squared"]
+        body = ["const double mk2 = (ex[ii] + ey[jj]) + ez[kk];",
+                "const double2 v = rhok[idx];",
+                "const double den = mk2 - m_squared;",
+                "sol[idx] = (mk2 < 0.0)",
+                "    ? make_double2((v.x * inv_n) / den, "
+                "(v.y * inv_n) / den)",
+                "    : make_double2(0.0, 0.0);"]
+    else:
+        raise ValueError(f"unknown k-space op {op!r}")
+    if flags:
+        raise TypeError(f"unexpected flags for {op}: {sorted(flags)}")
+    return params, body
+
+
+def kspace_source(op, kshape, **flags):
+    """HIP source of k-space kernel ``op`` (``"derivs"`` with
+    ``outs=``, ``"div_accum"`` with ``mu=`` and ``accumulate=``,
+    ``"poisson"``) over k-space ``kshape``.  Needs no device."""
+    params, body = _kspace_pieces(op, dict(flags))
+    head = (f"#define NKX {kshape[0]}\n"
+            f"#define NKY {kshape[1]}\n"
+            f"#define NKZ {kshape[2]}\n"
+            "#define VOLK ((long)NKX * NKY * NKZ)\n")
+    return head + KSPACE_KERNEL.format(
+        name=f"kspace_{op}", params=",\n    ".join(params),
+        body="\n    ".join(body))
+
+
+_kspace_cache = {}
+
+
+def _kspace_complex(name, t, kshape=None):
+    _check_tensor(name, t)
+    if t.dtype != torch.complex128:
+        raise TypeError(f"argument {name} has dtype {t.dtype}; the k-space "
+                        "kernels take complex128")
+    if t.dim() != 3 or (kshape is not None and tuple(t.shape) != kshape):
+        raise ValueError(f"argument {name} has shape {tuple(t.shape)}, "
+                         f"expected {kshape or 'a 3-D k-space array'}")
+    return tuple(t.shape)
+
+
+def _kspace_table(name, t, n):
+    _check_tensor(name, t)
+    if t.dtype != torch.float64:
+        raise TypeError(f"argument {name} has dtype {t.dtype}; the k-space "
+                        "tables are float64")
+    if t.dim() != 1 or t.numel() != n:
+        raise ValueError(f"argument {name} has shape {tuple(t.shape)}, "
+                         f"expected ({n},)")
+
+
+def _kspace_launch(op, kshape, ptrs, doubles, **flags):
+    """``flags`` as the entry points normalise them (``outs`` in
+    KSPACE_DERIV_OUTS order, ``mu`` an int, ``accumulate`` a bool)."""
+    key = (op, kshape) + tuple(sorted(flags.items()))
+    kid = _kspace_cache.get(key)
+    if kid is None:
+        kid = ext().jit_compile(kspace_source(op, kshape, **flags),
+                                f"kspace_{op}")
+        _kspace_cache[key] = kid
+    vol = int(np.prod(kshape))
+    if vol == 0:
+        return
+    ext().jit_launch(kid, (vol + 255) // 256, 1, 1, 256, 1, 1, 0, _stream(),
+                     ptrs, [], doubles)
+
+
+def kspace_derivs(fk, outs, k1, k2, inv_n):
+    """One launch: read ``fk`` once, write the requested spectral
+    derivatives of ``t = fk * inv_n``.
+
+    :arg outs: dict mapping any non-empty subset of ``pdx``, ``pdy``,
+        ``pdz`` (``i k1_mu t``) and ``lap`` (``-|k2|^2 t``) to contiguous
+        complex128 device tensors of ``fk``'s shape; none may be ``fk``.
+    :arg k1, k2: the three per-axis float64 tables, flat on the device.
+    """
+    if not isinstance(outs, dict) or not outs \
+            or set(outs) - set(KSPACE_DERIV_OUTS):
+        raise ValueError("outs must map a non-empty subset of "
+                         f"{KSPACE_DERIV_OUTS} to tensors")
+    kshape = _kspace_complex("fk", fk)
+    names = tuple(o for o in KSPACE_DERIV_OUTS if o in outs)
+    for o in names:
+        _kspace_complex(o, outs[o], kshape)
+        if outs[o].data_ptr() == fk.data_ptr():
+            raise ValueError(f"output {o} aliases fk")
+    if len({outs[o].data_ptr() for o in names}) != len(names):
+        raise ValueError("outputs alias each other")
+    for mu in range(3):
+        _kspace_table(f"k1[{mu}]", k1[mu], kshape[mu])
+        _kspace_table(f"k2[{mu}]", k2[mu], kshape[mu])
+    ptrs = [fk.data_ptr()] + [outs[o].data_ptr() for o in names]
+    ptrs += [k1[mu].data_ptr() for mu in range(3)
+             if f"pd{'xyz'[mu]}" in names]
+    if "lap" in names:
+        ptrs += [k.data_ptr() for k in k2]
+    _kspace_launch("derivs", kshape, ptrs, [float(inv_n)], outs=names)
+
+
+def kspace_div_accum(fk, div_k, k1_mu, mu, inv_n, accumulate):
+    """One launch: ``term = (i k1_mu fk) * inv_n``, stored to ``div_k``
+    (``accumulate=False``) or added to it.  ``div_k`` may not be ``fk``."""
+    kshape = _kspace_complex("fk", fk)
+    _kspace_complex("div_k", div_k, kshape)
+    if mu not in (0, 1, 2):
+        raise ValueError(f"mu must be 0, 1 or 2, got {mu}")
+    _kspace_table("k1_mu", k1_mu, kshape[mu])
+    if div_k.data_ptr() == fk.data_ptr():
+        raise ValueError("output div_k aliases fk")
+    _kspace_launch("div_accum", kshape,
+                   [fk.data_ptr(), div_k.data_ptr(), k1_mu.data_ptr()],
+                   [float(inv_n)], mu=mu, accumulate=bool(accumulate))
+
+
+def kspace_poisson(rhok, sol, ex, ey, ez, inv_n, m_squared):
+    """One launch: ``sol = (rhok * inv_n) / (mk2 - m_squared)`` where
+    ``mk2 = (ex[i] + ey[j]) + ez[k] < 0``, zero elsewhere (the k = 0 mode
+    is dropped for every mass).  The operation is purely per mode, so
+    ``sol`` may be the same tensor as ``rhok``.  ``m_squared`` is a
+    run-time argument: a new mass compiles nothing."""
+    kshape = _kspace_complex("rhok", rhok)
+    _kspace_complex("sol", sol, kshape)
+    for name, t, n in zip(("ex", "ey", "ez"), (ex, ey, ez), kshape):
+        _kspace_table(name, t, n)
+    _kspace_launch("poisson", kshape,
+                   [rhok.data_ptr(), sol.data_ptr(), ex.data_ptr(),
+                    ey.data_ptr(), ez.data_ptr()],
+                   [float(inv_n), float(m_squared)])
+
+
+# ---------------------------------------------------------------------------
 # AOT stencil kernels (csrc/derivs.hip)
 
 def _flat_fields(t, ndim_grid=3):

@@ -1,11 +1,16 @@
 """Spectral-collocation derivatives: FFT → ik-multiply → iFFT.
 
-Analogue of reference pystella/fourier/derivs.py:28-205.  The k-space
-multiplies are trivially bandwidth-bound torch ops fused per call; the
-FFTs are rocFFT (GPU) / FFTW-class (CPU) through torch.fft.
+Analogue of reference pystella/fourier/derivs.py:28-205.  On the GPU
+the k-space work of a call is one fused HIP kernel per slice
+(backend/hip.py ``kspace_derivs`` / ``kspace_div_accum``); on the CPU,
+for float32 transforms and with ``PYSTELLA_KSPACE=0`` it is a chain of
+torch ops.  The FFTs are rocFFT (GPU) / FFTW-class (CPU) through
+torch.fft.
 """
 
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -15,7 +20,15 @@ __all__ = ["SpectralCollocator"]
 
 class SpectralCollocator:
     """Exact spectral derivatives with the same call interface as
-    :class:`~pystella_amd.FiniteDifferencer`."""
+    :class:`~pystella_amd.FiniteDifferencer`.
+
+    On the fused GPU path the k-space outputs live in scratch buffers
+    owned by the collocator: allocated on first use, one per output of
+    the largest subset of ``lap``/``pdx``/``pdy``/``pdz`` ever requested
+    in one call, and reused across calls and slices.  That is at most
+    4 × 16 B × k-volume of device memory held for the collocator's
+    lifetime (4 GiB at 512³).
+    """
 
     def __init__(self, fft, dk):
         self.fft = fft
@@ -33,9 +46,29 @@ class SpectralCollocator:
             kk_mu[kk == 0] = 0.
             self.k1.append(torch.as_tensor(kk_mu, device=fft.fk.device))
 
+        # flat per-axis tables for the fused kernels, and the scratch
+        # buffers their outputs go to
+        self._k1_flat = [k.contiguous() for k in self.k1]
+        self._k2_flat = [k.contiguous() for k in self.k2]
+        self._scratch = []
+
         shape = (-1, 1, 1), (1, -1, 1), (1, 1, -1)
         self.k1 = [k.view(s) for k, s in zip(self.k1, shape)]
         self.k2 = [k.view(s) for k, s in zip(self.k2, shape)]
+
+    def _fused(self):
+        """The fused kernels take complex128 on the GPU; everything else
+        (CPU, float32 transforms, ``PYSTELLA_KSPACE=0``) runs the torch
+        chain."""
+        fk = self.fft.fk
+        return (isinstance(fk, torch.Tensor) and fk.is_cuda
+                and fk.dtype == torch.complex128 and fk.is_contiguous()
+                and os.environ.get("PYSTELLA_KSPACE") != "0")
+
+    def _get_scratch(self, n):
+        while len(self._scratch) < n:
+            self._scratch.append(torch.empty_like(self.fft.fk))
+        return self._scratch[:n]
 
     def _pd(self, fk, mu):
         return 1j * self.k1[mu] * fk
@@ -60,6 +93,23 @@ class SpectralCollocator:
         from itertools import product
         slices = list(product(*[range(n) for n in fx.shape[:-3]]))
         inv_n = 1.0 / self.grid_size
+
+        if self._fused():
+            from pystella_amd.backend import hip
+            outs = {name: out for name, out in (
+                ("lap", lap), ("pdx", pdx), ("pdy", pdy), ("pdz", pdz))
+                if out is not None}
+            if not outs:
+                return
+            bufs = dict(zip(outs, self._get_scratch(len(outs))))
+            for s in slices:
+                fk = self.fft.dft(fx[s])
+                hip.kspace_derivs(fk, bufs, self._k1_flat, self._k2_flat,
+                                  inv_n)
+                for name, out in outs.items():
+                    self.fft.idft(bufs[name], out[s])
+            return
+
         for s in slices:
             fk = self.fft.dft(fx[s]).clone() * inv_n
             if lap is not None:
@@ -78,6 +128,18 @@ class SpectralCollocator:
         from itertools import product
         slices = list(product(*[range(n) for n in vec.shape[:-4]]))
         inv_n = 1.0 / self.grid_size
+
+        if self._fused():
+            from pystella_amd.backend import hip
+            div_k, = self._get_scratch(1)
+            for s in slices:
+                for mu in range(3):
+                    fk = self.fft.dft(vec[s][mu])
+                    hip.kspace_div_accum(fk, div_k, self._k1_flat[mu], mu,
+                                         inv_n, accumulate=mu > 0)
+                self.fft.idft(div_k, div[s])
+            return
+
         for s in slices:
             div_k = None
             for mu in range(3):

@@ -4,9 +4,16 @@ Analogue of reference pystella/fourier/poisson.py:33-125.  The solve is
 implemented relative to the eigenvalues of a chosen second-difference
 stencil (``effective_k(k, dx)``), so solutions are consistent with the
 finite-difference Laplacian of the same order.
+
+On the GPU the k-space solve is one fused HIP kernel, in place on the
+transform's k-space array (backend/hip.py ``kspace_poisson``); on the
+CPU, for float32 transforms and with ``PYSTELLA_KSPACE=0`` it is a chain
+of torch ops.
 """
 
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -26,6 +33,8 @@ class SpectralPoissonSolver:
             kk_mu = effective_k(dk[mu] * kk.astype(np.float64), dx[mu])
             ks.append(torch.as_tensor(np.asarray(kk_mu, dtype=np.float64),
                                       device=dev))
+        # flat per-axis tables for the fused kernel
+        self._eig_flat = [k.contiguous() for k in ks]
         shape = (-1, 1, 1), (1, -1, 1), (1, 1, -1)
         # eigenvalues of the per-axis second difference (≤ 0); their sum
         # is −k²_eff
@@ -37,6 +46,14 @@ class SpectralPoissonSolver:
             fx = queue
             queue = None
         rhok = self.fft.dft(rho)
+        if (rhok.is_cuda and rhok.dtype == torch.complex128
+                and rhok.is_contiguous()
+                and os.environ.get("PYSTELLA_KSPACE") != "0"):
+            from pystella_amd.backend import hip
+            hip.kspace_poisson(rhok, rhok, *self._eig_flat,
+                               1.0 / self.grid_size, m_squared)
+            self.fft.idft(rhok, fx)
+            return fx
         denom = self.minus_k_squared - m_squared
         sol = torch.where(
             self.minus_k_squared < 0,
