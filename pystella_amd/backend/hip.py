@@ -467,18 +467,10 @@ class JitStageReduction:
             tname = lhs.name if hasattr(lhs, "name") else str(lhs)
             cg.tmp_names.add(tname)
             lines.append(f"const double {tname} = {cg.emit(rhs)};")
-        init_lines, combine_cases = [], []
-        for r, (expr, op) in enumerate(entries):
-            init_lines.append(f"acc[{r}] = {_OP_INIT[op]};")
-            comb = _OP_COMBINE[op]
-            val = cg.emit(expr)
-            lines.append(
-                "{ const double a = acc[%d]; const double b = %s; "
-                "acc[%d] = %s; }" % (r, val, r, comb))
-            combine_cases.append(f"(r == {r}) ? {comb} : ")
+        init_lines, acc_lines, combine = _reducer_pieces(cg, entries)
+        lines += acc_lines
         for lhs, rhs in map_dict.items():
             lines.append(f"{cg.emit(lhs)} = {cg.emit(rhs)};")
-        combine = "".join(combine_cases) + "0.0"
 
         ptr_params = ", ".join(
             f"double* __restrict__ {fa.name}" for fa in self.field_args)
@@ -488,7 +480,7 @@ class JitStageReduction:
 
         defines = geometry_defines(halo, rank_shape)
         defines += _tile_defines(tile, rank_shape)
-        defines += "#define COMBINE(r, a, b) (" + combine + ")\n"
+        defines += combine
         src = (STAGERED_TEMPLATE + REDUCTION_TAIL).format(
             defines=defines, preamble=PREAMBLE, nred=nred, name=name,
             params=params, init="\n    ".join(init_lines),
@@ -501,31 +493,7 @@ class JitStageReduction:
         self.nblk = self.grid[0] * self.grid[1] * self.grid[2]
         self._partials = None
 
-    def __call__(self, env):
-        dev = None
-        ptrs = []
-        want = getattr(self, "dtype", None)
-        for fa in self.field_args:
-            t = _check_tensor(fa.name, env[fa.name])
-            if want is None:
-                want = t.dtype
-            elif t.dtype != want:
-                raise TypeError(
-                    f"reduction argument '{fa.name}' has dtype "
-                    f"{t.dtype}, kernel expects {want}")
-            dev = t.device
-            ptrs.append(t.data_ptr())
-        nred = len(self.entries)
-        if (self._partials is None
-                or self._partials.device != dev
-                or self._partials.shape[1] != self.nblk):
-            self._partials = torch.empty((nred, self.nblk),
-                                         dtype=torch.float64, device=dev)
-        doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
-        ext().jit_launch(self.key, self.grid[0], self.grid[1],
-                         self.grid[2], self.block, 1, 1, 0, _stream(),
-                         ptrs + [self._partials.data_ptr()], [], doubles)
-        return self._finish(dev)
+    # __call__ and _finish are JitReduction's (assigned below it)
 
 
 def get_stage_reduction_kernel(map_dict, tmp_instructions, entries,
@@ -628,11 +596,12 @@ def wrap_star(fx, halo, wrap_axes):
 # ---------------------------------------------------------------------------
 # JIT'd simultaneous reductions
 
-REDUCTION_TAIL = """
+# Written once for every kernel that leaves per-block partials: ``{bid}``
+# declares the block's flat column ``bid`` in the partials buffer and
+# ``{stride}`` is that buffer's row length.
+PARTIALS_TAIL = """
     __shared__ double sd[TBZ * TBY];
-    const int nblk = gridDim.x * gridDim.y * gridDim.z;
-    const int bid = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x
-                    + blockIdx.x;
+    {bid}
     for (int r = 0; r < NRED; ++r) {{
         sd[threadIdx.x] = acc[r];
         __syncthreads();
@@ -643,11 +612,19 @@ REDUCTION_TAIL = """
             __syncthreads();
         }}
         if (threadIdx.x == 0)
-            partials[(long)r * nblk + bid] = sd[0];
+            partials[(long)r * {stride} + bid] = sd[0];
         __syncthreads();
     }}
 }}
 """
+
+# a launch that owns its partials buffer: one column per block of its grid
+_GRID_BID = """const int nblk = gridDim.x * gridDim.y * gridDim.z;
+    const int bid = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x
+                    + blockIdx.x;"""
+
+REDUCTION_TAIL = PARTIALS_TAIL.replace("{bid}", _GRID_BID).replace(
+    "{stride}", "nblk")
 
 REDUCTION_TEMPLATE = """{defines}
 {preamble}
@@ -674,6 +651,42 @@ _OP_COMBINE = {"sum": "(a + b)", "avg": "(a + b)", "prod": "(a * b)",
                "max": "fmax(a, b)", "min": "fmin(a, b)"}
 
 
+def _reducer_pieces(cg, entries, wide_scalars=False):
+    """(``acc[]`` init lines, per-site accumulate lines, the ``COMBINE``
+    define) of ``entries``.  The per-site values are emitted through
+    ``cg`` here, so the call's place among the caller's other emissions
+    fixes the reducers' place in the kernel's scalar parameter order.
+    ``wide_scalars`` brackets each value for a :class:`_LapCodegen`
+    (see there)."""
+    init_lines, acc_lines, combine_cases = [], [], []
+    for r, (expr, op) in enumerate(entries):
+        comb = _OP_COMBINE[op]
+        init_lines.append(f"acc[{r}] = {_OP_INIT[op]};")
+        if wide_scalars:
+            cg.wide_scalars = True
+        val = cg.emit(expr)
+        if wide_scalars:
+            cg.wide_scalars = False
+        acc_lines.append(
+            "{ const double a = acc[%d]; const double b = %s; "
+            "acc[%d] = %s; }" % (r, val, r, comb))
+        combine_cases.append(f"(r == {r}) ? {comb} : ")
+    combine = "".join(combine_cases) + "0.0"
+    return (init_lines, acc_lines,
+            f"#define COMBINE(r, a, b) ({combine})\n")
+
+
+def _partials_buffer(kern, dev):
+    """The [nred, nblk] per-block partials buffer that ``kern`` owns,
+    allocated anew when the device or the block count changed."""
+    p = kern._partials
+    if p is None or p.device != dev or p.shape[1] != kern.nblk:
+        p = kern._partials = torch.empty(
+            (len(kern.entries), kern.nblk), dtype=torch.float64,
+            device=dev)
+    return p
+
+
 class JitReduction:
     """Fused multi-quantity grid reduction → per-block partials,
     finished with torch ops + one packed allreduce by the caller."""
@@ -690,18 +703,7 @@ class JitReduction:
         nred = len(entries)
         cg = Codegen(field_args, halo, rank_shape)
 
-        init_lines = []
-        body_lines = []
-        combine_cases = []
-        for r, (expr, op) in enumerate(entries):
-            init_lines.append(f"acc[{r}] = {_OP_INIT[op]};")
-            comb = _OP_COMBINE[op]
-            val = cg.emit(expr)
-            body_lines.append(
-                "{ const double a = acc[%d]; const double b = %s; "
-                "acc[%d] = %s; }" % (r, val, r, comb))
-            combine_cases.append(f"(r == {r}) ? {comb} : ")
-        combine = "".join(combine_cases) + "0.0"
+        init_lines, body_lines, combine = _reducer_pieces(cg, entries)
 
         ptr_params = ", ".join(
             f"const real* __restrict__ {fa.name}"
@@ -712,7 +714,7 @@ class JitReduction:
 
         defines = geometry_defines(halo, rank_shape, rtype=_RTYPE[dtype])
         defines += _tile_defines(tile, rank_shape)
-        defines += ("#define COMBINE(r, a, b) (" + combine + ")\n")
+        defines += combine
         src = REDUCTION_TEMPLATE.format(
             defines=defines, preamble=PREAMBLE, nred=nred, name=name,
             params=params,
@@ -756,19 +758,15 @@ class JitReduction:
                     f"{t.dtype}, kernel expects {want}")
             dev = t.device
             ptrs.append(t.data_ptr())
-        nred = len(self.entries)
-        if (self._partials is None
-                or self._partials.device != dev
-                or self._partials.shape[1] != self.nblk):
-            self._partials = torch.empty((nred, self.nblk),
-                                         dtype=torch.float64, device=dev)
+        partials = _partials_buffer(self, dev)
         doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
         ext().jit_launch(self.key, self.grid[0], self.grid[1],
                          self.grid[2], self.block, 1, 1, 0, _stream(),
-                         ptrs + [self._partials.data_ptr()], [], doubles)
+                         ptrs + [partials.data_ptr()], [], doubles)
         return self._finish(dev)
 
 
+JitStageReduction.__call__ = JitReduction.__call__
 JitStageReduction._finish = JitReduction._finish
 
 
@@ -1588,45 +1586,49 @@ def _lap_stencil_pieces(h, dx, periodic, dtype=torch.float64):
 
 
 
-LAPRED_TEMPLATE = """{defines}
+# The x-march of every ring kernel, written once: ring fill, then per
+# site the ring load, the per-field Laplacian (stored if the form says
+# so), ``{body}`` and the ring shift, then the partials tail.  A form
+# (_FORM_GRID, _FORM_BOX, _FORM_SHELL) says where a block finds its
+# sites (``{prologue}`` yields k, j, i0 and i1; ``{kmax}``/``{jmax}``
+# bound k and j; ``{tables}`` precedes the kernel) and which column of
+# the partials buffer is its own (``{bid}``, ``{stride}``); _ring_source
+# fills it in.
+RING_MARCH_TEMPLATE = """{defines}
 {preamble}
 #define NRED {nred}
 #define NF {nf}
-extern "C" __global__ __launch_bounds__(TBZ * TBY) void {name}(
+{tables}extern "C" __global__ __launch_bounds__({bounds}) void {name}(
     {params})
 {{
     double acc[NRED];
     {init}
-    const int k = blockIdx.x * TBZ + (threadIdx.x % TBZ);
-    const int j = blockIdx.y * TBY + (threadIdx.x / TBZ);
-    const int i0 = blockIdx.z * XCHUNK;
-    const int i1 = (i0 + XCHUNK < NX) ? i0 + XCHUNK : NX;
-    if (k < NZ && j < NY) {{
+    {prologue}
+    if (k < {kmax} && j < {jmax}) {{
         const long sx = PSY * PSZ;
-        {R} ring[NF][2 * H + 1];
+        {wrap_decls}
+        {outer_decls}
         #pragma unroll
         for (int fld = 0; fld < NF; ++fld) {{
             const {R}* fp = {fname} + (long)fld * PVOL
                                + (long)(j + H) * PSZ + (k + H);
             #pragma unroll
-            for (int p = 0; p < 2 * H; ++p)
-                ring[fld][p] = fp[(long)(i0 + p) * sx];
+            for (int p = 0; p < 2 * H; ++p) {{
+                {ring_init}
+            }}
         }}
         for (int i = i0; i < i1; ++i) {{
-            {R} lapv[NF];
+            {site_decls}
+            {x_off}
             #pragma unroll
             for (int fld = 0; fld < NF; ++fld) {{
                 const {R}* fp = {fname} + (long)fld * PVOL
                                    + (long)(j + H) * PSZ + (k + H);
-                ring[fld][2 * H] = fp[(long)(i + 2 * H) * sx];
+                {ring_load}
                 const {R}* cp = fp + (long)(i + H) * sx;
                 {la_init}
                 {lap_terms}
-                lapv[fld] = la;
-#if STORE_LAP
-                {lapname}[(long)fld * UVOL + (((long)i * NY + j) * NZ + k)]
-                    = la;
-#endif
+                lapv[fld] = la;{store_lap}
             }}
             {body}
             #pragma unroll
@@ -1636,7 +1638,123 @@ extern "C" __global__ __launch_bounds__(TBZ * TBY) void {name}(
                     ring[fld][p] = ring[fld][p + 1];
         }}
     }}
-""" + REDUCTION_TAIL
+""" + PARTIALS_TAIL
+
+# ``{store_lap}`` of the kernels that can keep the Laplacian
+_STORE_LAP = """
+#if STORE_LAP
+                {lapname}[(long)fld * UVOL + (((long)i * NY + j) * NZ + k)]
+                    = la;
+#endif"""
+
+# the whole grid, one launch with a partials buffer of its own
+_FORM_GRID = dict(
+    tables="",
+    prologue="""const int k = blockIdx.x * TBZ + (threadIdx.x % TBZ);
+    const int j = blockIdx.y * TBY + (threadIdx.x / TBZ);
+    const int i0 = blockIdx.z * XCHUNK;
+    const int i1 = (i0 + XCHUNK < NX) ? i0 + XCHUNK : NX;""",
+    kmax="NZ", jmax="NY", bid=_GRID_BID, stride="nblk")
+
+# a box passed as ints; sub-box launches of the same kernel write
+# disjoint slices (from column bid0) of one shared partials buffer
+_FORM_BOX = dict(
+    tables="",
+    prologue="""const int k = k0b + blockIdx.x * TBZ + (threadIdx.x % TBZ);
+    const int j = j0b + blockIdx.y * TBY + (threadIdx.x / TBZ);
+    const int i0 = i0b + blockIdx.z * XCHUNK;
+    const int i1 = (i0 + XCHUNK < i1b) ? i0 + XCHUNK : i1b;""",
+    kmax="k1b", jmax="j1b",
+    bid="""const int bid = bid0 + (blockIdx.z * gridDim.y + blockIdx.y)
+                    * gridDim.x + blockIdx.x;""",
+    stride="nblkT")
+
+# Multi-box "shell" form: ONE launch covers all boundary slabs of a
+# rank (separate thin-slab launches are latency-bound at ~1 wave/CU
+# each and serialize).  Box bounds and per-box block-grid tables are
+# baked as constant arrays; blocks decode their (box, tile) from the
+# flat blockIdx.x, and the reduction tail indexes partials by the flat
+# block id.
+_SHELL_TABLES = """#define NBOX {nbox}
+__constant__ int sh_k0[NBOX] = {{ {k0s} }};
+__constant__ int sh_k1[NBOX] = {{ {k1s} }};
+__constant__ int sh_j0[NBOX] = {{ {j0s} }};
+__constant__ int sh_j1[NBOX] = {{ {j1s} }};
+__constant__ int sh_i0[NBOX] = {{ {i0s} }};
+__constant__ int sh_i1[NBOX] = {{ {i1s} }};
+__constant__ int sh_gz[NBOX] = {{ {gzs} }};
+__constant__ int sh_gy[NBOX] = {{ {gys} }};
+__constant__ int sh_blk0[NBOX] = {{ {blk0s} }};
+"""
+
+_FORM_SHELL = dict(
+    prologue="""const int bflat = (int)blockIdx.x;
+    int box = 0;
+    #pragma unroll
+    for (int b = 1; b < NBOX; ++b) box += (bflat >= sh_blk0[b]);
+    const int lb = bflat - sh_blk0[box];
+    const int bz = lb % sh_gz[box];
+    const int by = (lb / sh_gz[box]) % sh_gy[box];
+    const int bx = lb / (sh_gz[box] * sh_gy[box]);
+    const int k = sh_k0[box] + bz * TBZ + (int)(threadIdx.x % TBZ);
+    const int j = sh_j0[box] + by * TBY + (int)(threadIdx.x / TBZ);
+    const int i0 = sh_i0[box] + bx * XCHUNK;
+    const int i1 = (i0 + XCHUNK < sh_i1[box]) ? i0 + XCHUNK
+                                              : sh_i1[box];""",
+    kmax="sh_k1[box]", jmax="sh_j1[box]",
+    bid="const int bid = bid0 + bflat;", stride="nblkT")
+
+
+def _ring_source(parts, form, **over):
+    """RING_MARCH_TEMPLATE filled with a kernel's ``parts`` for
+    ``form``.  Where ``lapv[]`` is declared goes with the form: the
+    shell form has it outside the x-loop, the others inside, and the
+    compiler's register allocation follows the place (the GW shell
+    kernels at MINW 2 come out different if it moves)."""
+    lapv = "{R} lapv[NF];".format(**parts)
+    ring = "{R} ring[NF][2 * H + 1];".format(**parts)
+    if form is _FORM_SHELL:
+        decls = dict(outer_decls=f"{lapv}\n        {ring}", site_decls="")
+    else:
+        decls = dict(outer_decls=ring, site_decls=lapv)
+    return RING_MARCH_TEMPLATE.format(
+        **{**parts, **form, **decls, **over})
+
+
+def _march_pieces(f_name, halo, dx, periodic, dtype):
+    """(RING_MARCH_TEMPLATE's stencil fields, the LAPC0 define) for the
+    stencil field ``f_name``."""
+    h = max(halo) if isinstance(halo, (tuple, list)) else halo
+    (wrap_decls, lap_terms, lapc0, x_off, ring_load, ring_init,
+     la_init) = _lap_stencil_pieces(h, dx, periodic, dtype)
+    return dict(
+        R=_real_name(dtype), fname=f_name,
+        wrap_decls="\n        ".join(wrap_decls), x_off=x_off,
+        ring_load=ring_load, ring_init=ring_init, la_init=la_init,
+        lap_terms="\n                ".join(lap_terms),
+    ), _lapc0_define(lapc0, dtype)
+
+
+def _ring_params(cg, field_args, f_name, lap_name, R, store_lap=False,
+                 state=False, ints=None):
+    """(pointer names, their field args, parameter list) of a ring
+    kernel: stencil field first, the Laplacian if stored, the other
+    spatial fields sorted, the device-state buffer if any, partials,
+    ints, then the run-time scalars ``cg`` collected so far."""
+    ptr_names = [f_name] + ([lap_name] if store_lap else []) + sorted(
+        fa.name for fa in field_args
+        if fa.spatial and fa.name not in (f_name, lap_name))
+    by_name = {fa.name: fa for fa in field_args}
+    ptr_args = [by_name[n] for n in ptr_names if n in by_name]
+    params = [f"{R}* __restrict__ {n}" for n in ptr_names]
+    if state:
+        ptr_names.append("state")
+        params.append("const double* __restrict__ state")
+    params.append("double* __restrict__ partials")
+    if ints:
+        params.append(ints)
+    params += [f"double {c}" for c, _ in cg.scalars]
+    return ptr_names, ptr_args, ", ".join(params)
 
 
 class _LapCodegen(Codegen):
@@ -1678,67 +1796,37 @@ class JitLapReduction:
 
     def __init__(self, entries, field_args, scalar_names, halo, rank_shape,
                  dx, nf, f_name="f", lap_name="lap_f", name="lapred_map",
-                 tile=(64, 4, 64), store_lap=True,
-                 periodic=(False, False, False), dtype=torch.float64,
+                 tile=(64, 4, 64), store_lap=True, dtype=torch.float64,
                  compile=True):
-        from pystella_amd.derivs import _LAP_COEFS
         self.rank_shape = tuple(rank_shape)
         self.tile = tile
         self.dtype = dtype
         self.state_map = None
-        R = _real_name(dtype)
         self.store_lap = store_lap
         self.entries = entries
-        h = max(halo) if isinstance(halo, (tuple, list)) else halo
         self.nf = nf
+        # the stencil reads the halo on every axis
+        self.periodic = (False, False, False)
+        march, lapc0 = _march_pieces(f_name, halo, dx, self.periodic, dtype)
+        R = march["R"]
         cg = _LapCodegen(field_args, halo, rank_shape, f_name, lap_name)
         if R == "real":
             cg.one = "real(1.0)"
-
-        init_lines, body_lines, combine_cases = [], [], []
-        for r, (expr, op) in enumerate(entries):
-            init_lines.append(f"acc[{r}] = {_OP_INIT[op]};")
-            comb = _OP_COMBINE[op]
-            cg.wide_scalars = R == "real"
-            val = cg.emit(expr)
-            cg.wide_scalars = False
-            body_lines.append(
-                "{ const double a = acc[%d]; const double b = %s; "
-                "acc[%d] = %s; }" % (r, val, r, comb))
-            combine_cases.append(f"(r == {r}) ? {comb} : ")
-        combine = "".join(combine_cases) + "0.0"
-
-        # Laplacian stencil terms with dx baked in
-        self.periodic = tuple(periodic)
-        (wrap_decls, lap_terms, lapc0, x_off, ring_load,
-         ring_init, la_init) = _lap_stencil_pieces(h, dx, periodic, dtype)
-
-        # pointer params: stencil field first, then lap (if stored),
-        # then the rest
-        self.ptr_names = ([f_name, lap_name] if store_lap
-                          else [f_name]) + sorted(
-            fa.name for fa in field_args
-            if fa.spatial and fa.name not in (f_name, lap_name))
-        by_name = {fa.name: fa for fa in field_args}
-        self.field_args = [by_name[n] for n in self.ptr_names if n in by_name]
-        ptr_params = ", ".join(
-            f"{R}* __restrict__ {n}" for n in self.ptr_names)
-        dbl_params = ", ".join(f"double {c}" for c, _ in cg.scalars)
-        params = ", ".join(x for x in (
-            ptr_params, "double* __restrict__ partials", dbl_params) if x)
+        init_lines, body_lines, combine = _reducer_pieces(
+            cg, entries, wide_scalars=R == "real")
+        self.ptr_names, self.field_args, params = _ring_params(
+            cg, field_args, f_name, lap_name, R, store_lap=store_lap)
 
         defines = geometry_defines(halo, rank_shape, rtype=_RTYPE[dtype])
         defines += _tile_defines(tile, rank_shape)
-        defines += f"#define COMBINE(r, a, b) ({combine})\n"
-        defines += _lapc0_define(lapc0, dtype)
+        defines += combine + lapc0
         defines += f"#define STORE_LAP {1 if store_lap else 0}\n"
-        src = LAPRED_TEMPLATE.format(
+        src = _ring_source(dict(
             defines=defines, preamble=PREAMBLE, nred=len(entries), nf=nf,
-            name=name, params=params, fname=f_name, lapname=lap_name,
-            R=R, la_init=la_init,
+            bounds="TBZ * TBY", name=name, params=params,
             init="\n    ".join(init_lines),
-            lap_terms="\n                ".join(lap_terms),
-            body="\n            ".join(body_lines))
+            store_lap=_STORE_LAP.format(lapname=lap_name),
+            body="\n            ".join(body_lines), **march), _FORM_GRID)
         self.source = src
         self.scalar_keys = [k for _, k in cg.scalars]
         # compile=False: source only (inspectable without a device)
@@ -1752,89 +1840,12 @@ class JitLapReduction:
 
     def __call__(self, env):
         ptrs, dev = _kernel_ptrs(self, env)
-        nred = len(self.entries)
-        if (self._partials is None
-                or self._partials.device != dev
-                or self._partials.shape[1] != self.nblk):
-            self._partials = torch.empty((nred, self.nblk),
-                                         dtype=torch.float64, device=dev)
+        partials = _partials_buffer(self, dev)
         doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
         ext().jit_launch(self.key, self.grid[0], self.grid[1],
                          self.grid[2], self.block, 1, 1, 0, _stream(),
-                         ptrs + [self._partials.data_ptr()], [], doubles)
+                         ptrs + [partials.data_ptr()], [], doubles)
         return self._finish(dev)
-
-
-# Reduction tail with runtime partials geometry (sub-box launches of
-# the same kernel write disjoint slices of one shared partials buffer).
-REDUCTION_TAIL_BOX = """
-    __shared__ double sd[TBZ * TBY];
-    const int bid = bid0 + (blockIdx.z * gridDim.y + blockIdx.y)
-                    * gridDim.x + blockIdx.x;
-    for (int r = 0; r < NRED; ++r) {{
-        sd[threadIdx.x] = acc[r];
-        __syncthreads();
-        for (int s = (TBZ * TBY) / 2; s > 0; s >>= 1) {{
-            if ((int)threadIdx.x < s)
-                sd[threadIdx.x] = COMBINE(r, sd[threadIdx.x],
-                                          sd[threadIdx.x + s]);
-            __syncthreads();
-        }}
-        if (threadIdx.x == 0)
-            partials[(long)r * nblkT + bid] = sd[0];
-        __syncthreads();
-    }}
-}}
-"""
-
-LAPSTAGE_TEMPLATE = """{defines}
-{preamble}
-#define NRED {nred}
-#define NF {nf}
-extern "C" __global__ __launch_bounds__(TBZ * TBY, MINW) void {name}(
-    {params})
-{{
-    double acc[NRED];
-    {init}
-    const int k = k0b + blockIdx.x * TBZ + (threadIdx.x % TBZ);
-    const int j = j0b + blockIdx.y * TBY + (threadIdx.x / TBZ);
-    const int i0 = i0b + blockIdx.z * XCHUNK;
-    const int i1 = (i0 + XCHUNK < i1b) ? i0 + XCHUNK : i1b;
-    if (k < k1b && j < j1b) {{
-        const long sx = PSY * PSZ;
-        {wrap_decls}
-        {R} ring[NF][2 * H + 1];
-        #pragma unroll
-        for (int fld = 0; fld < NF; ++fld) {{
-            const {R}* fp = {fname} + (long)fld * PVOL
-                               + (long)(j + H) * PSZ + (k + H);
-            #pragma unroll
-            for (int p = 0; p < 2 * H; ++p) {{
-                {ring_init}
-            }}
-        }}
-        for (int i = i0; i < i1; ++i) {{
-            {R} lapv[NF];
-            {x_off}
-            #pragma unroll
-            for (int fld = 0; fld < NF; ++fld) {{
-                const {R}* fp = {fname} + (long)fld * PVOL
-                                   + (long)(j + H) * PSZ + (k + H);
-                {ring_load}
-                const {R}* cp = fp + (long)(i + H) * sx;
-                {la_init}
-                {lap_terms}
-                lapv[fld] = la;
-            }}
-            {body}
-            #pragma unroll
-            for (int fld = 0; fld < NF; ++fld)
-                #pragma unroll
-                for (int p = 0; p < 2 * H; ++p)
-                    ring[fld][p] = ring[fld][p + 1];
-        }}
-    }}
-""" + REDUCTION_TAIL_BOX
 
 
 class _NTLapCodegen(_LapCodegen):
@@ -1848,11 +1859,10 @@ class _NTLapCodegen(_LapCodegen):
         self.preload = {}       # (name, lin) -> register var
         self.store_ctx = False
         self.state_map = state_map or {}
-        self.sectioned_lapv = False
 
     def scalar_param(self, name, idx=()):
         # state scalars are hoisted into per-thread registers once at
-        # kernel entry (st_<name>, see JitLapStage state prologue)
+        # kernel entry (st_<name>, see _state_prologue)
         if name in self.state_map and not idx:
             return f"std_{name}" if self.wide_scalars else f"st_{name}"
         return super().scalar_param(name, idx)
@@ -1864,141 +1874,108 @@ class _NTLapCodegen(_LapCodegen):
             reg = self.preload.get((f.name, lin))
             if reg is not None:
                 return reg
-        if (self.sectioned_lapv and f.is_spatial and not any(f.shift)
-                and len(outer_idx) <= 1 and f.name == self.lap_name):
-            lin = int(outer_idx[0]) if outer_idx else 0
-            return f"lapv_{lin}"
         return super().field_access(f, outer_idx)
 
 
-# Multi-box "shell" form: ONE launch covers all boundary slabs of a
-# rank (separate thin-slab launches are latency-bound at ~1 wave/CU
-# each and serialize).  Box bounds and per-box block-grid tables are
-# baked as constant arrays; blocks decode their (box, tile) from the
-# flat blockIdx.x, and the reduction tail indexes partials by the flat
-# block id.
-LAPSTAGE_SHELL_TEMPLATE = """{defines}
-{preamble}
-#define NRED {nred}
-#define NF {nf}
-#define NBOX {nbox}
-__constant__ int sh_k0[NBOX] = {{ {k0s} }};
-__constant__ int sh_k1[NBOX] = {{ {k1s} }};
-__constant__ int sh_j0[NBOX] = {{ {j0s} }};
-__constant__ int sh_j1[NBOX] = {{ {j1s} }};
-__constant__ int sh_i0[NBOX] = {{ {i0s} }};
-__constant__ int sh_i1[NBOX] = {{ {i1s} }};
-__constant__ int sh_gz[NBOX] = {{ {gzs} }};
-__constant__ int sh_gy[NBOX] = {{ {gys} }};
-__constant__ int sh_blk0[NBOX] = {{ {blk0s} }};
-extern "C" __global__ __launch_bounds__(TBZ * TBY, MINW) void {name}(
-    {params})
-{{
-    double acc[NRED];
-    {init}
-    const int bflat = (int)blockIdx.x;
-    int box = 0;
-    #pragma unroll
-    for (int b = 1; b < NBOX; ++b) box += (bflat >= sh_blk0[b]);
-    const int lb = bflat - sh_blk0[box];
-    const int bz = lb % sh_gz[box];
-    const int by = (lb / sh_gz[box]) % sh_gy[box];
-    const int bx = lb / (sh_gz[box] * sh_gy[box]);
-    const int k = sh_k0[box] + bz * TBZ + (int)(threadIdx.x % TBZ);
-    const int j = sh_j0[box] + by * TBY + (int)(threadIdx.x / TBZ);
-    const int i0 = sh_i0[box] + bx * XCHUNK;
-    const int i1 = (i0 + XCHUNK < sh_i1[box]) ? i0 + XCHUNK
-                                              : sh_i1[box];
-    if (k < sh_k1[box] && j < sh_j1[box]) {{
-        const long sx = PSY * PSZ;
-        {wrap_decls}
-        {R} lapv[NF];
-        {R} ring[NF][2 * H + 1];
-        #pragma unroll
-        for (int fld = 0; fld < NF; ++fld) {{
-            const {R}* fp = {fname} + (long)fld * PVOL
-                               + (long)(j + H) * PSZ + (k + H);
-            #pragma unroll
-            for (int p = 0; p < 2 * H; ++p) {{
-                {ring_init}
-            }}
-        }}
-        for (int i = i0; i < i1; ++i) {{
-            {x_off}
-            #pragma unroll
-            for (int fld = 0; fld < NF; ++fld) {{
-                const {R}* fp = {fname} + (long)fld * PVOL
-                                   + (long)(j + H) * PSZ + (k + H);
-                {ring_load}
-                const {R}* cp = fp + (long)(i + H) * sx;
-                {la_init}
-                {lap_terms}
-                lapv[fld] = la;
-            }}
-            {body}
-            #pragma unroll
-            for (int fld = 0; fld < NF; ++fld)
-                #pragma unroll
-                for (int p = 0; p < 2 * H; ++p)
-                    ring[fld][p] = ring[fld][p + 1];
-        }}
-    }}
-    __shared__ double sd[TBZ * TBY];
-    const int bid = bid0 + bflat;
-    for (int r = 0; r < NRED; ++r) {{
-        sd[threadIdx.x] = acc[r];
-        __syncthreads();
-        for (int s = (TBZ * TBY) / 2; s > 0; s >>= 1) {{
-            if ((int)threadIdx.x < s)
-                sd[threadIdx.x] = COMBINE(r, sd[threadIdx.x],
-                                          sd[threadIdx.x + s]);
-            __syncthreads();
-        }}
-        if (threadIdx.x == 0)
-            partials[(long)r * nblkT + bid] = sd[0];
-        __syncthreads();
-    }}
-}}
-"""
+def _nt_preloads(field_args, lap_name, exprs):
+    """Sorted (name, component) of every component of the unpadded
+    streaming arrays (the RK k-arrays) that ``exprs`` read: each is
+    preloaded once per site with a nontemporal load."""
+    from pystella_amd.field import Field, Subscript, iter_exprs, walk_expr
+    nt_names = {fa.name for fa in field_args
+                if fa.spatial and not fa.padded and fa.name != lap_name
+                and len(fa.outer_shape) <= 1}
+    used = set()
+
+    def visit(x):
+        if isinstance(x, Subscript) and isinstance(x.aggregate, Field) \
+                and x.aggregate.name in nt_names and len(x.index) == 1 \
+                and isinstance(x.index[0], int):
+            used.add((x.aggregate.name, int(x.index[0])))
+        elif isinstance(x, Field) and x.name in nt_names and not x.shape:
+            used.add((x.name, 0))
+
+    for e in iter_exprs(exprs):
+        walk_expr(e, visit)
+    return sorted(used)
 
 
-LAPSTAGE_SEC_TEMPLATE = """{defines}
-{preamble}
-#define NRED {nred}
-#define NF {nf}
-extern "C" __global__ __launch_bounds__(TBZ * TBY, MINW) void {name}(
-    {params})
-{{
-    double acc[NRED];
-    {init}
-    const int k = k0b + blockIdx.x * TBZ + (threadIdx.x % TBZ);
-    const int j = j0b + blockIdx.y * TBY + (threadIdx.x / TBZ);
-    const int i0 = i0b + blockIdx.z * XCHUNK;
-    const int i1 = (i0 + XCHUNK < i1b) ? i0 + XCHUNK : i1b;
-    if (k < k1b && j < j1b) {{
-        const long sx = PSY * PSZ;
-        {wrap_decls}
-        {R} ring[NF][2 * H + 1];
-        #pragma unroll
-        for (int fld = 0; fld < NF; ++fld) {{
-            const {R}* fp = {fname} + (long)fld * PVOL
-                               + (long)(j + H) * PSZ + (k + H);
-            #pragma unroll
-            for (int p = 0; p < 2 * H; ++p) {{
-                {ring_init}
-            }}
-        }}
-        for (int i = i0; i < i1; ++i) {{
-            {x_off}
-            {site_body}
-            #pragma unroll
-            for (int fld = 0; fld < NF; ++fld)
-                #pragma unroll
-                for (int p = 0; p < 2 * H; ++p)
-                    ring[fld][p] = ring[fld][p + 1];
-        }}
-    }}
-""" + REDUCTION_TAIL_BOX
+def _preload_decl(R, nm, lin):
+    off = "(((long)i*NY + j)*NZ + k)"
+    if lin:
+        off = f"({lin}L*UVOL + {off})"
+    return (f"const {R} pl_{nm}_{lin} = "
+            f"__builtin_nontemporal_load(&{nm}[{off}]);")
+
+
+def _store_lines(cg, items, nt):
+    lines = []
+    for lhs, rhs in items:
+        val = cg.emit(rhs)
+        cg.store_ctx = True
+        dst = cg.emit(lhs)
+        cg.store_ctx = False
+        if nt:
+            lines.append(f"__builtin_nontemporal_store({val}, &{dst});")
+        else:
+            lines.append(f"{dst} = {val};")
+    return lines
+
+
+def _stage_site_body(cg, R, tmp_items, entries, store_items, preloads,
+                     nt, guard_stores, guard_scalar):
+    """(site lines, ``acc[]`` init lines, COMBINE define) of a stage
+    kernel.  Per site: k-array preloads, temporaries, the reducers
+    (so they see the input state), then the stores."""
+    from pystella_amd.field import Subscript
+    for lhs, _ in tmp_items:
+        cg.tmp_names.add(lhs.name if hasattr(lhs, "name") else str(lhs))
+    lines = []
+    for nm, lin in preloads:
+        cg.preload[(nm, lin)] = f"pl_{nm}_{lin}"
+        lines.append(_preload_decl(R, nm, lin))
+    for lhs, rhs in tmp_items:
+        tname = lhs.name if hasattr(lhs, "name") else str(lhs)
+        lines.append(f"const {R} {tname} = {cg.emit(rhs)};")
+    acc_init, acc_lines, combine = _reducer_pieces(
+        cg, entries, wide_scalars=R == "real")
+    lines += acc_lines
+
+    def guarded(lhs):
+        f = lhs.aggregate if isinstance(lhs, Subscript) else lhs
+        return getattr(f, "name", None) in guard_stores
+
+    if guard_stores and guard_scalar is not None:
+        # runtime-skippable stores (dead last-stage k writes, see
+        # fusion.py): identical compiled form across stages, one
+        # uniform scalar branch around the block
+        lines += _store_lines(
+            cg, [(l, r) for l, r in store_items if not guarded(l)], nt)
+        late = [(l, r) for l, r in store_items if guarded(l)]
+        if late:
+            cond = cg.scalar_param(guard_scalar)
+            zero = "0.0" if R == "double" else "real(0.0)"
+            lines.append(f"if ({cond} != {zero}) {{")
+            lines += _store_lines(cg, late, nt)
+            lines.append("}")
+    else:
+        lines += _store_lines(cg, store_items, nt)
+    return lines, acc_init, combine
+
+
+def _state_prologue(state_map, R):
+    """Kernel-entry reads of the device-state scalars into registers."""
+    lines = []
+    for nm, sidx in sorted((state_map or {}).items()):
+        if R == "double":
+            lines.append(f"const double st_{nm} = state[{sidx}];")
+        else:
+            # narrowed once at kernel entry, so the per-site
+            # expressions that use it stay in real; the reducers
+            # take the double (see _LapCodegen.wide_scalars)
+            lines.append(f"const double std_{nm} = state[{sidx}];")
+            lines.append(f"const real st_{nm} = real(std_{nm});")
+    return lines
 
 
 class JitLapStage:
@@ -2013,16 +1990,9 @@ class JitLapStage:
     (see fusion.StencilRKStepper).
 
     For large stencil families (the 6-component GW h_ij sector), the
-    flat per-site emission keeps all 6 Laplacians + 12 k-preloads +
-    ring live simultaneously — 256 VGPRs, 2 waves/SIMD, ~4.2 TB/s
-    (measured round 1).  ``section_size`` restructures the per-site
-    body into per-component SECTIONS (ring load → Laplacian → RHS →
-    k update → stores for one component, then the next) separated by
-    ``__builtin_amdgcn_sched_barrier(0)`` so the register allocator
-    sees short, non-overlapping live ranges; occupancy goes up at the
-    price of less in-thread ILP (hidden instead by the extra waves).
-    Set ``PYSTELLA_SECTIONS=<n>`` to force a section size (0 = flat
-    emission)."""
+    per-site emission keeps all 6 Laplacians + 12 k-preloads + ring
+    live simultaneously — 256 VGPRs, 2 waves/SIMD, ~4.2 TB/s
+    (measured round 1)."""
 
     # tile candidates, best-first for large grids; smaller tiles win on
     # small per-rank grids (multi-GPU strong scaling) where the big
@@ -2066,12 +2036,9 @@ class JitLapStage:
                  scalar_names, halo, rank_shape, dx, nf, f_name="f",
                  lap_name="lap_f", name="rk_lapstage", tile=None,
                  nt=True, state_map=None, min_waves=1,
-                 periodic=(False, False, False), section_size=None,
+                 periodic=(False, False, False),
                  guard_stores=frozenset(), guard_scalar=None,
                  dtype=torch.float64, compile=True):
-        import os as _os
-        from pystella_amd.field import (
-            Field, Subscript, Variable, is_number, iter_exprs, walk_expr)
         if tile is None:
             tile = self.pick_tile(rank_shape)
         self.rank_shape = tuple(rank_shape)
@@ -2080,368 +2047,45 @@ class JitLapStage:
         self.shmem = 0
         self.tile = tile
         self.dtype = dtype
-        # per-site type: arrays, ring, Laplacian, RHS and the 2N update;
-        # acc[], the LDS tree, partials and the state buffer stay double
-        R = _real_name(dtype)
         self.entries = entries
-        h = max(halo) if isinstance(halo, (tuple, list)) else halo
         self.nf = nf
         self.state_map = state_map
+        self.periodic = tuple(periodic)
+        # per-site type R: arrays, ring, Laplacian, RHS and the 2N update;
+        # acc[], the LDS tree, partials and the state buffer stay double
+        march, lapc0 = _march_pieces(f_name, halo, dx, periodic, dtype)
+        R = march["R"]
         cg = _NTLapCodegen(field_args, halo, rank_shape, f_name, lap_name,
                            state_map=state_map)
         if R == "real":
             cg.one = "real(1.0)"
 
         tmp_items = list((tmp_instructions or {}).items())
-        store_items = list(map_dict.items())
-        tmp_set = set()
-        for lhs, _ in tmp_items:
-            tname = lhs.name if hasattr(lhs, "name") else str(lhs)
-            tmp_set.add(tname)
-            cg.tmp_names.add(tname)
-
-        # ---- section-size selection -----------------------------------
-        env = _os.environ.get("PYSTELLA_SECTIONS")
-        if env is not None and env != "":
-            section_size = int(env)
-        entries_trivial = all(is_number(e) for e, _ in entries)
-        if section_size is None:
-            section_size = 0    # default pending A/B measurement
-
-        def _store_comp(lhs):
-            if isinstance(lhs, Subscript) and lhs.index \
-                    and isinstance(lhs.index[0], (int, np.integer)):
-                return int(lhs.index[0])
-            return None
-
-        comps = [_store_comp(lhs) for lhs, _ in store_items]
-        sectioned = bool(
-            section_size and section_size < nf and entries_trivial
-            and all(c is not None and 0 <= c < nf for c in comps))
-
-        # ---- NT preload discovery --------------------------------------
-        nt_used = set()
-        if nt:
-            # preload every read component of the unpadded streaming
-            # arrays (the RK k-arrays) with a nontemporal load
-            nt_names = {fa.name for fa in field_args
-                        if fa.spatial and not fa.padded
-                        and fa.name != lap_name
-                        and len(fa.outer_shape) <= 1}
-
-            def visit(x):
-                if isinstance(x, Subscript) and \
-                        isinstance(x.aggregate, Field) and \
-                        x.aggregate.name in nt_names and \
-                        len(x.index) == 1 and \
-                        isinstance(x.index[0], int):
-                    nt_used.add((x.aggregate.name, int(x.index[0])))
-                elif isinstance(x, Field) and x.name in nt_names \
-                        and not x.shape:
-                    nt_used.add((x.name, 0))
-
-            for e in iter_exprs([[r for _, r in tmp_items],
-                                 [e for e, _ in entries]]):
-                walk_expr(e, visit)
-            for nm, lin in sorted(nt_used):
-                cg.preload[(nm, lin)] = f"pl_{nm}_{lin}"
-
-        def _preload_decl(nm, lin):
-            off = "(((long)i*NY + j)*NZ + k)"
-            if lin:
-                off = f"({lin}L*UVOL + {off})"
-            return (f"const {R} pl_{nm}_{lin} = "
-                    f"__builtin_nontemporal_load(&{nm}[{off}]);")
-
-        # ---- shared emission helpers -----------------------------------
-        self.periodic = tuple(periodic)
-        (wrap_decls, lap_terms, lapc0, x_off, ring_load,
-         ring_init, la_init) = _lap_stencil_pieces(h, dx, periodic, dtype)
-
-        def _emit_tmps(items, out):
-            for lhs, rhs in items:
-                tname = lhs.name if hasattr(lhs, "name") else str(lhs)
-                out.append(f"const {R} {tname} = {cg.emit(rhs)};")
-
-        def _emit_stores(items, out):
-            for lhs, rhs in items:
-                val = cg.emit(rhs)
-                cg.store_ctx = True
-                dst = cg.emit(lhs)
-                cg.store_ctx = False
-                if nt:
-                    out.append(
-                        f"__builtin_nontemporal_store({val}, &{dst});")
-                else:
-                    out.append(f"{dst} = {val};")
-
-        def _fp_decl(lin):
-            return (f"    const {R}* fp = {f_name} + (long)fld * PVOL"
-                    f" + (long)(j + H) * PSZ + (k + H);")
-
-        def _stencil_block(lin, out):
-            out.append(f"{R} lapv_{lin};")
-            out.append("{")
-            out.append(f"    const int fld = {lin};")
-            out.append(_fp_decl(lin))
-            out.append("    " + ring_load)
-            out.append(f"    const {R}* cp = fp + (long)(i + H) * sx;")
-            out.append("    " + la_init)
-            for t in lap_terms:
-                out.append("    " + t)
-            out.append(f"    lapv_{lin} = la;")
-            out.append("}")
-
-        def _ring_load_block(lin, out):
-            out.append("{")
-            out.append(f"    const int fld = {lin};")
-            out.append(_fp_decl(lin))
-            out.append("    " + ring_load)
-            out.append("}")
-
-        init_lines, combine_cases = [], []
-        for nm, sidx in sorted((state_map or {}).items()):
-            if R == "double":
-                init_lines.append(
-                    f"const double st_{nm} = state[{sidx}];")
-            else:
-                # narrowed once at kernel entry, so the per-site
-                # expressions that use it stay in real; the reducers
-                # take the double (see _LapCodegen.wide_scalars)
-                init_lines.append(
-                    f"const double std_{nm} = state[{sidx}];")
-                init_lines.append(
-                    f"const real st_{nm} = real(std_{nm});")
-        for r, (expr, op) in enumerate(entries):
-            init_lines.append(f"acc[{r}] = {_OP_INIT[op]};")
-            combine_cases.append(f"(r == {r}) ? {_OP_COMBINE[op]} : ")
-        combine = "".join(combine_cases) + "0.0"
-
-        def _entry_lines(out):
-            for r, (expr, op) in enumerate(entries):
-                cg.wide_scalars = R == "real"
-                val = cg.emit(expr)
-                cg.wide_scalars = False
-                out.append(
-                    "{ const double a = acc[%d]; const double b = %s; "
-                    "acc[%d] = %s; }" % (r, val, r, _OP_COMBINE[op]))
-
-        def _vars_of(expr):
-            out = set()
-
-            def v(x):
-                if isinstance(x, Variable):
-                    out.add(x.name)
-
-            walk_expr(expr, v)
-            return out
-
-        def _lap_lins(exprs):
-            lins = set()
-
-            def v(x):
-                if isinstance(x, Subscript) \
-                        and isinstance(x.aggregate, Field) \
-                        and x.aggregate.name == lap_name and x.index \
-                        and isinstance(x.index[0], (int, np.integer)):
-                    lins.add(int(x.index[0]))
-                elif isinstance(x, Field) and x.name == lap_name:
-                    lins.add(0)
-
-            for e in exprs:
-                walk_expr(e, v)
-            return lins
-
-        def _nt_in(exprs):
-            found = set()
-
-            def v(x):
-                if isinstance(x, Subscript) \
-                        and isinstance(x.aggregate, Field) \
-                        and len(x.index) == 1 \
-                        and isinstance(x.index[0], int):
-                    key = (x.aggregate.name, int(x.index[0]))
-                    if key in cg.preload:
-                        found.add(key)
-                elif isinstance(x, Field) and not x.shape \
-                        and (x.name, 0) in cg.preload:
-                    found.add((x.name, 0))
-
-            for e in exprs:
-                walk_expr(e, v)
-            return found
-
-        if sectioned:
-            # per-component sections: ring load + Laplacian + tmps +
-            # stores for one component at a time, sched_barrier-fenced
-            cg.sectioned_lapv = True
-            n_sec = (nf + section_size - 1) // section_size
-            sec_stores = [[] for _ in range(n_sec)]
-            for (lhs, rhs), c in zip(store_items, comps):
-                sec_stores[c // section_size].append((lhs, rhs))
-
-            deps = {}
-            for lhs, rhs in tmp_items:
-                tname = lhs.name if hasattr(lhs, "name") else str(lhs)
-                deps[tname] = _vars_of(rhs) & tmp_set
-            need = {t: set() for t in tmp_set}
-            for s in range(n_sec):
-                frontier = set()
-                for _, rhs in sec_stores[s]:
-                    frontier |= _vars_of(rhs) & tmp_set
-                seen = set()
-                while frontier:
-                    t = frontier.pop()
-                    if t in seen:
-                        continue
-                    seen.add(t)
-                    need[t].add(s)
-                    frontier |= deps.get(t, set())
-            pro_tmps = []
-            sec_tmps = [[] for _ in range(n_sec)]
-            for lhs, rhs in tmp_items:
-                tname = lhs.name if hasattr(lhs, "name") else str(lhs)
-                regs = need.get(tname, set())
-                if len(regs) == 1:
-                    sec_tmps[next(iter(regs))].append((lhs, rhs))
-                else:
-                    pro_tmps.append((lhs, rhs))
-
-            region_exprs = [
-                [r for _, r in sec_tmps[s]] + [r for _, r in sec_stores[s]]
-                for s in range(n_sec)]
-            pro_exprs = ([r for _, r in pro_tmps]
-                         + [e for e, _ in entries])
-            used_by = {lin: set() for lin in range(nf)}
-            for s in range(n_sec):
-                for lin in _lap_lins(region_exprs[s]):
-                    used_by.setdefault(lin, set()).add(s)
-            for lin in _lap_lins(pro_exprs):
-                used_by.setdefault(lin, set()).add(-1)
-            lin_place = {}
-            for lin in range(nf):
-                regs = used_by.get(lin, set())
-                if len(regs) == 1 and -1 not in regs:
-                    lin_place[lin] = next(iter(regs))
-                elif regs:
-                    lin_place[lin] = -1
-                else:
-                    lin_place[lin] = None    # ring-load only
-
-            nt_region = {key: set() for key in nt_used}
-            for s in range(n_sec):
-                for key in _nt_in(region_exprs[s]):
-                    nt_region[key].add(s)
-            for key in _nt_in(pro_exprs):
-                nt_region[key].add(-1)
-
-            # PYSTELLA_SECTION_MASK: instruction categories allowed to
-            # cross the section fences (sched_barrier mask; e.g. 0x20
-            # lets VMEM reads prefetch across sections while keeping
-            # arithmetic sectioned)
-            mask = int(_os.environ.get("PYSTELLA_SECTION_MASK", "0"), 0)
-            fence = f"__builtin_amdgcn_sched_barrier({mask});"
-            body = []
-            for lin in range(nf):
-                if lin_place[lin] is None:
-                    _ring_load_block(lin, body)
-                elif lin_place[lin] == -1:
-                    _stencil_block(lin, body)
-            for key in sorted(k for k, v in nt_region.items()
-                              if len(v) != 1 or -1 in v):
-                body.append(_preload_decl(*key))
-            _emit_tmps(pro_tmps, body)
-            _entry_lines(body)
-            for s in range(n_sec):
-                body.append(fence)
-                for lin in range(nf):
-                    if lin_place[lin] == s:
-                        _stencil_block(lin, body)
-                for key in sorted(k for k, v in nt_region.items()
-                                  if v == {s}):
-                    body.append(_preload_decl(*key))
-                _emit_tmps(sec_tmps[s], body)
-                _emit_stores(sec_stores[s], body)
-            body.append(fence)
-            lines = body
-        else:
-            lines = []
-            for nm, lin in sorted(nt_used):
-                lines.append(_preload_decl(nm, lin))
-            _emit_tmps(tmp_items, lines)
-            _entry_lines(lines)
-
-            def _lhs_name(lhs):
-                f = lhs.aggregate if isinstance(lhs, Subscript) else lhs
-                return getattr(f, "name", None)
-
-            if guard_stores and guard_scalar is not None:
-                # runtime-skippable stores (dead last-stage k writes,
-                # see fusion.py): identical compiled form across
-                # stages, one uniform scalar branch around the block
-                normal = [(l, r) for l, r in store_items
-                          if _lhs_name(l) not in guard_stores]
-                guarded = [(l, r) for l, r in store_items
-                           if _lhs_name(l) in guard_stores]
-                _emit_stores(normal, lines)
-                if guarded:
-                    cond = cg.scalar_param(guard_scalar)
-                    zero = "0.0" if R == "double" else "real(0.0)"
-                    lines.append(f"if ({cond} != {zero}) {{")
-                    _emit_stores(guarded, lines)
-                    lines.append("}")
-            else:
-                _emit_stores(store_items, lines)
-        self.sectioned = sectioned
-
-        # pointer params: stencil field first, then every other spatial
-        # field referenced by the statements or reducers, then the
-        # optional device-state scalar buffer
-        self.ptr_names = [f_name] + sorted(
-            fa.name for fa in field_args
-            if fa.spatial and fa.name not in (f_name, lap_name))
-        by_name = {fa.name: fa for fa in field_args}
-        self.field_args = [by_name[n] for n in self.ptr_names
-                           if n in by_name]
-        ptr_params = ", ".join(
-            f"{R}* __restrict__ {n}" for n in self.ptr_names)
-        if state_map:
-            self.ptr_names.append("state")
-            ptr_params += ", const double* __restrict__ state"
-        int_params = ("const int k0b, const int k1b, const int j0b, "
-                      "const int j1b, const int i0b, const int i1b, "
-                      "const int nblkT, const int bid0")
-        dbl_params = ", ".join(f"double {c}" for c, _ in cg.scalars)
-        params = ", ".join(x for x in (
-            ptr_params, "double* __restrict__ partials", int_params,
-            dbl_params) if x)
+        preloads = _nt_preloads(
+            field_args, lap_name,
+            [[r for _, r in tmp_items], [e for e, _ in entries]]) \
+            if nt else []
+        lines, acc_init, combine = _stage_site_body(
+            cg, R, tmp_items, entries, list(map_dict.items()), preloads,
+            nt, guard_stores, guard_scalar)
+        self.ptr_names, self.field_args, params = _ring_params(
+            cg, field_args, f_name, lap_name, R, state=bool(state_map),
+            ints="const int k0b, const int k1b, const int j0b, "
+                 "const int j1b, const int i0b, const int i1b, "
+                 "const int nblkT, const int bid0")
 
         defines = geometry_defines(halo, rank_shape, rtype=_RTYPE[dtype])
         defines += _tile_defines(tile, rank_shape)
         defines += f"#define MINW {min_waves}\n"
-        defines += f"#define COMBINE(r, a, b) ({combine})\n"
-        defines += _lapc0_define(lapc0, dtype)
-        if sectioned:
-            src = LAPSTAGE_SEC_TEMPLATE.format(
-                defines=defines, preamble=PREAMBLE, nred=len(entries),
-                nf=nf, name=name, params=params, fname=f_name,
-                init="\n    ".join(init_lines),
-                wrap_decls="\n        ".join(wrap_decls),
-                x_off=x_off, ring_init=ring_init, R=R,
-                site_body="\n            ".join(lines))
-            self._shell_parts = None
-        else:
-            fmt = dict(
-                defines=defines, preamble=PREAMBLE, nred=len(entries),
-                nf=nf, name=name, params=params, fname=f_name,
-                init="\n    ".join(init_lines),
-                wrap_decls="\n        ".join(wrap_decls),
-                x_off=x_off, ring_load=ring_load, ring_init=ring_init,
-                R=R, la_init=la_init,
-                lap_terms="\n                ".join(lap_terms),
-                body="\n            ".join(lines))
-            src = LAPSTAGE_TEMPLATE.format(**fmt)
-            self._shell_parts = fmt
+        defines += combine + lapc0
+        # everything but the form: the shell form is rendered per set
+        # of boxes (_shell_build)
+        self._parts = dict(
+            defines=defines, preamble=PREAMBLE, nred=len(entries), nf=nf,
+            bounds="TBZ * TBY, MINW", name=name, params=params,
+            init="\n    ".join(_state_prologue(state_map, R) + acc_init),
+            store_lap="", body="\n            ".join(lines), **march)
+        src = _ring_source(self._parts, _FORM_BOX)
         self._shell_cache = {}
         self.source = src
         self.scalar_keys = [k for _, k in cg.scalars]
@@ -2489,41 +2133,43 @@ class JitLapStage:
         return cached
 
     def _shell_build(self, boxes):
-        if self._shell_parts is None:
-            raise RuntimeError("shell form unavailable (sectioned)")
         grids = [self._box_geometry(b)[0] for b in boxes]
         nbs = [g[0] * g[1] * g[2] for g in grids]
         blk0 = [0]
         for n in nbs[:-1]:
             blk0.append(blk0[-1] + n)
-        fmt = dict(self._shell_parts)
-        fmt["name"] = fmt["name"] + "_shell"
-        fmt["nbox"] = len(boxes)
 
         def ints(vals):
             return ", ".join(str(int(v)) for v in vals)
 
-        src = LAPSTAGE_SHELL_TEMPLATE.format(
+        tables = _SHELL_TABLES.format(
+            nbox=len(boxes),
             k0s=ints(b[4] for b in boxes), k1s=ints(b[5] for b in boxes),
             j0s=ints(b[2] for b in boxes), j1s=ints(b[3] for b in boxes),
             i0s=ints(b[0] for b in boxes), i1s=ints(b[1] for b in boxes),
             gzs=ints(g[0] for g in grids), gys=ints(g[1] for g in grids),
-            blk0s=ints(blk0), **fmt)
-        return src, fmt["name"], sum(nbs)
+            blk0s=ints(blk0))
+        name = self._parts["name"] + "_shell"
+        src = _ring_source(self._parts, _FORM_SHELL, name=name,
+                           tables=tables)
+        return src, name, sum(nbs)
 
     def shell_nblk(self, boxes):
         return self._get_shell(tuple(boxes))[1]
+
+    def _launch(self, key, grid, env, ptrs, partials, ints):
+        doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
+        ext().jit_launch(key, grid[0], grid[1], grid[2], self.block, 1, 1,
+                         self.shmem, _stream(),
+                         ptrs + [partials.data_ptr()], ints, doubles)
 
     def launch_shell(self, env, boxes, partials, bid0, nblk_tot):
         """ONE launch covering every box in ``boxes`` (the rank's
         boundary slabs); per-block partials land flat at ``bid0``."""
         ptrs, _ = _kernel_ptrs(self, env)
         kid, total = self._get_shell(tuple(boxes))
-        doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
-        ext().jit_launch(kid, total, 1, 1, self.block, 1, 1,
-                         self.shmem, _stream(),
-                         ptrs + [partials.data_ptr()],
-                         [0, 0, 0, 0, 0, 0, nblk_tot, bid0], doubles)
+        self._launch(kid, (total, 1, 1), env, ptrs, partials,
+                     [0, 0, 0, 0, 0, 0, nblk_tot, bid0])
 
     def launch_box(self, env, box, partials, bid0, nblk_tot):
         """Launch over a sub-box, writing this launch's per-block
@@ -2531,32 +2177,22 @@ class JitLapStage:
         buffer [nred, nblk_tot].  Stream-ordered, no host sync."""
         ptrs, _ = _kernel_ptrs(self, env)
         grid, ints = self._box_geometry(box)
-        doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
-        ext().jit_launch(self.key, grid[0], grid[1], grid[2],
-                         self.block, 1, 1, self.shmem, _stream(),
-                         ptrs + [partials.data_ptr()],
-                         ints + [nblk_tot, bid0], doubles)
+        self._launch(self.key, grid, env, ptrs, partials,
+                     ints + [nblk_tot, bid0])
 
     def launch_only(self, env):
         """Full-grid launch without finishing the reduction; returns the
         raw per-block partials tensor [nred, nblk] (stream-ordered, no
         host synchronization)."""
-        _, dev = _kernel_ptrs(self, env)
-        nred = len(self.entries)
-        if (self._partials is None
-                or self._partials.device != dev
-                or self._partials.shape[1] != self.nblk):
-            self._partials = torch.empty((nred, self.nblk),
-                                         dtype=torch.float64, device=dev)
+        ptrs, dev = _kernel_ptrs(self, env)
+        partials = _partials_buffer(self, dev)
         nx, ny, nz = self.rank_shape
-        self.launch_box(env, (0, nx, 0, ny, 0, nz), self._partials,
-                        0, self.nblk)
-        return self._partials
+        self._launch(self.key, self.grid, env, ptrs, partials,
+                     [0, nz, 0, ny, 0, nx, self.nblk, 0])
+        return partials
 
     def __call__(self, env):
-        _, dev = _kernel_ptrs(self, env)
-        self.launch_only(env)
-        return self._finish(dev)
+        return self._finish(self.launch_only(env).device)
 
 
 FRIEDMANN_TEMPLATE = """

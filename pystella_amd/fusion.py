@@ -850,9 +850,7 @@ class DeviceFriedmannLoop:
             # slab time at the 256^3 N=8-rank proxy).
             # PYSTELLA_SHELL=0 falls back to per-slab launches.
             use_shell = (bool(slabs) and f.is_cuda
-                         and os.environ.get("PYSTELLA_SHELL") != "0"
-                         and getattr(kerns[0][0], "_shell_parts", None)
-                         is not None)
+                         and os.environ.get("PYSTELLA_SHELL") != "0")
             slab_kerns = ([] if use_shell
                           else [self._slab_kerns(smap, kerns, b)
                                 for b in slabs])

@@ -1,8 +1,8 @@
-"""Emit the GW hij ring-stage kernel source (flat and sectioned forms)
-and cross-compile each with hipcc --offload-arch=gfx950 to validate
-syntax and report the register allocation (no GPU needed).
+"""Emit the GW hij ring-stage kernel sources and cross-compile each
+with hipcc --offload-arch=gfx950 to validate syntax and report the
+register allocation (no GPU needed).
 
-Usage: python tools/emit_gw_kernel.py [--sections N] [--no-compile]
+Usage: python tools/emit_gw_kernel.py [--no-compile] [--dump DIR]
 """
 
 import argparse
@@ -17,7 +17,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
-def build_sources(sections):
+def build_sources():
     """Return {kernel_name: source} for the bench --gws stage kernels,
     built exactly as DeviceFriedmannLoop would build them."""
     import pystella_amd as ps
@@ -80,8 +80,6 @@ def build_sources(sections):
 
         m = smap._map
         rs = m._infer_rank_shape(env)
-        if sections is not None:
-            os.environ["PYSTELLA_SECTIONS"] = str(sections)
         from pystella_amd.backend.hip import get_lap_stage_kernel
         for (rk_o, tmp_o, red_o, f_name, nf), fargs in zip(
                 smap.ring, smap._ring_field_args):
@@ -93,7 +91,6 @@ def build_sources(sections):
                 state_map={"a": 0, "hubble": 4})
     finally:
         hip.ext = orig_ext
-        os.environ.pop("PYSTELLA_SECTIONS", None)
     return captured
 
 
@@ -126,13 +123,12 @@ def compile_one(name, src, keep=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--sections", type=int, default=None)
     ap.add_argument("--no-compile", action="store_true")
     ap.add_argument("--dump", default=None,
                     help="write each source to DIR/<name>.hip")
     p = ap.parse_args()
 
-    srcs = build_sources(p.sections)
+    srcs = build_sources()
     print("kernels built:", sorted(srcs))
     for name, src in sorted(srcs.items()):
         if p.dump:
