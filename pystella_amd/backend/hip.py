@@ -1923,11 +1923,10 @@ def _store_lines(cg, items, nt):
 
 
 def _stage_site_body(cg, R, tmp_items, entries, store_items, preloads,
-                     nt, guard_stores, guard_scalar):
+                     nt):
     """(site lines, ``acc[]`` init lines, COMBINE define) of a stage
     kernel.  Per site: k-array preloads, temporaries, the reducers
     (so they see the input state), then the stores."""
-    from pystella_amd.field import Subscript
     for lhs, _ in tmp_items:
         cg.tmp_names.add(lhs.name if hasattr(lhs, "name") else str(lhs))
     lines = []
@@ -1940,26 +1939,7 @@ def _stage_site_body(cg, R, tmp_items, entries, store_items, preloads,
     acc_init, acc_lines, combine = _reducer_pieces(
         cg, entries, wide_scalars=R == "real")
     lines += acc_lines
-
-    def guarded(lhs):
-        f = lhs.aggregate if isinstance(lhs, Subscript) else lhs
-        return getattr(f, "name", None) in guard_stores
-
-    if guard_stores and guard_scalar is not None:
-        # runtime-skippable stores (dead last-stage k writes, see
-        # fusion.py): identical compiled form across stages, one
-        # uniform scalar branch around the block
-        lines += _store_lines(
-            cg, [(l, r) for l, r in store_items if not guarded(l)], nt)
-        late = [(l, r) for l, r in store_items if guarded(l)]
-        if late:
-            cond = cg.scalar_param(guard_scalar)
-            zero = "0.0" if R == "double" else "real(0.0)"
-            lines.append(f"if ({cond} != {zero}) {{")
-            lines += _store_lines(cg, late, nt)
-            lines.append("}")
-    else:
-        lines += _store_lines(cg, store_items, nt)
+    lines += _store_lines(cg, store_items, nt)
     return lines, acc_init, combine
 
 
@@ -2037,7 +2017,6 @@ class JitLapStage:
                  lap_name="lap_f", name="rk_lapstage", tile=None,
                  nt=True, state_map=None, min_waves=1,
                  periodic=(False, False, False),
-                 guard_stores=frozenset(), guard_scalar=None,
                  dtype=torch.float64, compile=True):
         if tile is None:
             tile = self.pick_tile(rank_shape)
@@ -2067,7 +2046,7 @@ class JitLapStage:
             if nt else []
         lines, acc_init, combine = _stage_site_body(
             cg, R, tmp_items, entries, list(map_dict.items()), preloads,
-            nt, guard_stores, guard_scalar)
+            nt)
         self.ptr_names, self.field_args, params = _ring_params(
             cg, field_args, f_name, lap_name, R, state=bool(state_map),
             ints="const int k0b, const int k1b, const int j0b, "
@@ -2292,15 +2271,12 @@ def get_lap_stage_kernel(map_dict, tmp_instructions, entries, field_args,
                          f_name="f", lap_name="lap_f",
                          name="rk_lapstage", tile=None, nt=True,
                          state_map=None, periodic=(False, False, False),
-                         guard_stores=frozenset(), guard_scalar=None,
                          dtype=torch.float64, compile=True):
     return JitLapStage(map_dict, tmp_instructions, entries, field_args,
                        scalar_names, halo, rank_shape, dx, nf,
                        f_name=f_name, lap_name=lap_name, name=name,
                        tile=tile, nt=nt, state_map=state_map,
-                       periodic=periodic, guard_stores=guard_stores,
-                       guard_scalar=guard_scalar, dtype=dtype,
-                       compile=compile)
+                       periodic=periodic, dtype=dtype, compile=compile)
 
 
 def get_lap_reduction_kernel(entries, field_args, scalar_names, halo,

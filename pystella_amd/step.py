@@ -44,6 +44,22 @@ def _field_of(key):
     raise ValueError("rhs_dict keys must be Fields or subscripted Fields")
 
 
+def _rhs_dict_of(input):
+    """The ``{unknown: time derivative}`` dict of a dict, a Sector or a
+    list of Sectors."""
+    from pystella_amd.sectors import Sector
+    if isinstance(input, Sector):
+        return dict(input.rhs_dict)
+    if isinstance(input, list):
+        rhs_dict = {}
+        for s in input:
+            rhs_dict.update(s.rhs_dict)
+        return rhs_dict
+    if isinstance(input, dict):
+        return dict(input)
+    raise TypeError("input must be a dict, Sector, or list thereof")
+
+
 def _prepend_index(expr, q):
     """Prepend outer index ``q`` to every Field access in ``expr``
     (the classical-RK copy axis; reference step.py:202-212)."""
@@ -76,18 +92,7 @@ class Stepper:
 
     def __init__(self, input, dt=None, halo_shape=0, rank_shape=None,
                  **kwargs):
-        from pystella_amd.sectors import Sector
-        if isinstance(input, Sector):
-            self.rhs_dict = dict(input.rhs_dict)
-        elif isinstance(input, list):
-            self.rhs_dict = {}
-            for s in input:
-                self.rhs_dict.update(s.rhs_dict)
-        elif isinstance(input, dict):
-            self.rhs_dict = dict(input)
-        else:
-            raise TypeError("input must be a dict, Sector, or list thereof")
-
+        self.rhs_dict = _rhs_dict_of(input)
         self.dt = dt
         self.halo_shape = halo_shape
         self.rank_shape = rank_shape

@@ -1315,6 +1315,112 @@ def test_device_loop_full_shell_split_gpu(grid_shape=(24, 24, 24)):
 
 
 @requires_gpu
+def test_host_and_device_use_of_one_stepper_gpu(monkeypatch,
+                                                grid_shape=(16, 12, 20)):
+    """One stepper driven by a device loop, then by the host loop, then
+    by a device loop and the host loop again, each from the same seeded
+    state: the stage maps keep the kernels of both launch forms apart
+    (the host form takes a and H by value, the device form reads the
+    state buffer), so every phase computes what it computes alone and
+    each form is compiled once.  The grid runs the one-wave (32,2,8)
+    tile with partly filled blocks on every axis."""
+    from pystella_amd.backend.hip import JitLapStage
+    from pystella_amd.fusion import (
+        DeviceFriedmannLoop, FusedLaplacianReduction, StencilRKStepper)
+    from pystella_amd.sectors import get_rho_and_p
+    for name in ("PYSTELLA_TILE", "PYSTELLA_PERIODIC", "PYSTELLA_SHELL",
+                 "PYSTELLA_NO_OVERLAP", "PYSTELLA_KEEP_LASTK"):
+        monkeypatch.delenv(name, raising=False)
+    h = 2
+    decomp = ps.DomainDecomposition((1, 1, 1), h, rank_shape=grid_shape)
+    dx = (0.3, 0.31, 0.29)
+    dt = 0.005
+    gsize = float(np.prod(grid_shape))
+
+    def pot(f):
+        return f[0]**2 / 2 + f[0]**2 * f[1]**2 / 4
+
+    sector = ps.ScalarSector(2, potential=pot)
+    derivs = ps.FiniteDifferencer(decomp, h, dx, rank_shape=grid_shape)
+    pad = tuple(n + 2 * h for n in grid_shape)
+    torch.manual_seed(91)
+    f0 = (0.2 + 0.01 * torch.rand((2,) + pad, dtype=torch.float64)).cuda()
+    d0 = (0.01 * torch.rand((2,) + pad, dtype=torch.float64)).cuda()
+    decomp.share_halos(f0)
+    red = FusedLaplacianReduction(
+        decomp, sector, derivs, halo_shape=h, callback=get_rho_and_p,
+        rank_shape=grid_shape, grid_size=gsize, store_lap=False)
+    e0 = red(f=f0, dfdt=d0, a=np.ones(1))["total"]
+
+    built = []
+    real_init = JitLapStage.__init__
+
+    def counting_init(self, *args, **kwargs):
+        built.append(kwargs.get("name"))
+        real_init(self, *args, **kwargs)
+
+    monkeypatch.setattr(JitLapStage, "__init__", counting_init)
+
+    def make_stepper():
+        return StencilRKStepper(ps.LowStorageRK54, [sector], derivs,
+                                halo_shape=h, rank_shape=grid_shape,
+                                dt=dt, reducers=sector, grid_size=gsize,
+                                callback=get_rho_and_p)
+
+    def fresh():
+        arrays = {"f": f0.clone(), "dfdt": d0.clone(),
+                  "f_next": torch.zeros_like(f0)}
+        return arrays, ps.Expansion(e0, ps.LowStorageRK54)
+
+    def device_step(st):
+        arrays, ex = fresh()
+        dl = DeviceFriedmannLoop(st, decomp, ex, gsize, dt)
+        n0 = len(built)
+        dl.step(arrays)
+        state = dl.read_state()
+        for s in range(st.num_stages):
+            kern, = st._stepper.steps[s]._hip_kernel
+            assert kern.state_map == DeviceFriedmannLoop.STATE_MAP
+            assert tuple(kern.tile) == (32, 2, 8)
+        return arrays, state, len(built) - n0
+
+    def host_step(st):
+        arrays, ex = fresh()
+        n0 = len(built)
+        for s in range(st.num_stages):
+            e_in = st(s, a=ex.a, hubble=ex.hubble, **arrays)
+            for name in st.pingpong:
+                arrays[name], arrays[f"{name}_next"] = \
+                    arrays[f"{name}_next"], arrays[name]
+                decomp.share_halos(arrays[name])
+            ex.step(s, e_in["total"], e_in["pressure"], dt)
+        torch.cuda.synchronize()
+        for s in range(st.num_stages):
+            kern, = st._stepper.steps[s]._hip_kernel
+            assert kern.state_map is None
+        return arrays, float(ex.a[0]), len(built) - n0
+
+    S = make_stepper()
+    dev_a, state_a, n_a = device_step(S)
+    host_b, a_b, n_b = host_step(S)
+    dev_c, state_c, n_c = device_step(S)
+    host_d, a_d, n_d = host_step(S)
+    host_t, a_t, n_t = host_step(make_stepper())
+
+    for name in ("f", "dfdt"):
+        assert torch.equal(dev_a[name], dev_c[name]), name
+        assert torch.equal(host_b[name], host_t[name]), name
+        assert torch.equal(host_d[name], host_t[name]), name
+    assert state_a["a"] == state_c["a"]
+    assert state_a["energy"] == state_c["energy"]
+    assert a_b == a_t and a_d == a_t
+    # one kernel per stage and launch form, at its first use; going
+    # back and forth compiles nothing
+    assert (n_a, n_b, n_t) == (S.num_stages,) * 3, (n_a, n_b, n_t)
+    assert (n_c, n_d) == (0, 0), (n_c, n_d)
+
+
+@requires_gpu
 def test_smoother_star_wrap_bit_equality(n=32, h=1):
     """The smoothing loop's fused face-wrap fast path (star operators,
     fully-local decomp) is bit-identical to full corner-propagating

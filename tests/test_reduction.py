@@ -333,6 +333,83 @@ def test_device_loop_region_partition():
         assert (count == 1).all(), (proc_shape, count.min(), count.max())
 
 
+def test_device_loop_periodic_axes(monkeypatch):
+    """Which axes the device loop's stage kernels read periodically
+    in-kernel: the non-decomposed ones, all of them up to 17 M sites
+    per rank and none above unless PYSTELLA_PERIODIC forces them; never
+    when a family reads shifted padded fields (inlined gradients need
+    filled halos).  Only the product of the rank shape is looked at;
+    nothing is allocated."""
+    from pystella_amd.fusion import DeviceFriedmannLoop, StencilRKStepper
+    from pystella_amd.sectors import get_rho_and_p
+
+    grid_shape = (16, 12, 20)
+    h = 2
+    decomp = ps.DomainDecomposition((1, 1, 1), h, rank_shape=grid_shape)
+    sector = ps.ScalarSector(2, potential=lambda f: f[0]**2 / 2)
+    derivs = ps.FiniteDifferencer(decomp, h, (0.3, 0.3, 0.3),
+                                  rank_shape=grid_shape)
+
+    def stepper(sectors, **kwargs):
+        return StencilRKStepper(
+            ps.LowStorageRK54, sectors, derivs, halo_shape=h,
+            rank_shape=grid_shape, dt=0.01, reducers=sector,
+            grid_size=float(np.prod(grid_shape)),
+            callback=get_rho_and_p, **kwargs)
+
+    class _D:
+        pass
+
+    def loop_for(st, proc_shape):
+        # the real constructor with a stand-in decomp: it only keeps it
+        loop = DeviceFriedmannLoop(st, _D(), None, 1.0, 0.01)
+        loop.decomp.proc_shape = proc_shape
+        return loop
+
+    F, T = False, True
+    small, large = (256, 256, 256), (512, 512, 128)
+    assert np.prod(small) < 17_000_000 < np.prod(large)
+    # {PYSTELLA_PERIODIC: {proc_shape: (below threshold, above)}}
+    table = {
+        None: {(1, 1, 1): ((T, T, T), (F, F, F)),
+               (2, 1, 1): ((F, T, T), (F, F, F)),
+               (1, 1, 2): ((T, T, F), (F, F, F))},
+        "0": {(1, 1, 1): ((F, F, F), (F, F, F)),
+              (2, 1, 1): ((F, F, F), (F, F, F)),
+              (1, 1, 2): ((F, F, F), (F, F, F))},
+        "1": {(1, 1, 1): ((T, T, T), (T, T, T)),
+              (2, 1, 1): ((F, T, T), (F, T, T)),
+              (1, 1, 2): ((T, T, F), (T, T, F))},
+        "z": {(1, 1, 1): ((F, F, T), (F, F, T)),
+              (2, 1, 1): ((F, F, T), (F, F, T)),
+              (1, 1, 2): ((F, F, F), (F, F, F))},
+        "yz": {(1, 1, 1): ((F, T, T), (F, T, T)),
+               (2, 1, 1): ((F, T, T), (F, T, T)),
+               (1, 1, 2): ((F, T, F), (F, T, F))},
+    }
+    scalar = stepper([sector])
+    gw = stepper([sector, ps.TensorPerturbationSector([sector])],
+                 inline_grad=True)
+    for force, rows in table.items():
+        if force is None:
+            monkeypatch.delenv("PYSTELLA_PERIODIC", raising=False)
+        else:
+            monkeypatch.setenv("PYSTELLA_PERIODIC", force)
+        for proc_shape, expected in rows.items():
+            loop, loop_gw = (loop_for(st, proc_shape)
+                             for st in (scalar, gw))
+            for rank_shape, want in zip((small, large), expected):
+                for smap in scalar._stepper.steps:
+                    got = loop._periodic_axes(smap, rank_shape)
+                    assert tuple(got) == want, \
+                        (force, proc_shape, rank_shape, got)
+                # the tensor family reads the scalars' shifted values
+                got = loop_gw._periodic_axes(gw._stepper.steps[1],
+                                             rank_shape)
+                assert tuple(got) == (F, F, F), \
+                    (force, proc_shape, rank_shape, got)
+
+
 def test_field_statistics_min_max(grid_shape=(12, 12, 12)):
     """FieldStatistics with max_min=True (reference reduction.py:284-302)."""
     h = 1

@@ -265,7 +265,7 @@ def test_fp32_mixed_dtypes_refused_before_launch(monkeypatch):
     # a float32 kernel handed a float64 array names the argument
     arrays["dfdt"] = arrays["dfdt"].float()
     kerns = st._stepper.steps[0].ring_kernels(GRID, torch.float32)
-    env = dict(arrays, dt=DT, store_k=1.0, rk_a0=0.0, a=1.0, hubble=0.0,
+    env = dict(arrays, dt=DT, rk_a0=0.0, a=1.0, hubble=0.0,
                f_tmp=torch.zeros((2,) + GRID, device="cuda"),
                dfdt_tmp=torch.zeros((2,) + GRID, dtype=torch.float64,
                                     device="cuda"))

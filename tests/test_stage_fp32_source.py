@@ -260,7 +260,7 @@ def _env(h, dtypes):
            "f_tmp": torch.zeros((2,) + GRID, dtype=dtypes["f_tmp"]),
            "dfdt_tmp": torch.zeros((2,) + GRID, dtype=dtypes["dfdt_tmp"]),
            "state": torch.zeros(8, dtype=torch.float64),
-           "dt": DT, "store_k": 1.0, "rk_a0": 0.0}
+           "dt": DT, "rk_a0": 0.0}
     return env
 
 

@@ -191,7 +191,6 @@ def test_stage_halo_orders(h, tile, periodic, monkeypatch):
 LAUNCH_FORMS = {
     "shell": {},
     "slabs": {"PYSTELLA_SHELL": "0"},
-    "slab_tiles": {"PYSTELLA_SHELL": "0", "PYSTELLA_SLAB_TILES": "1"},
 }
 
 

@@ -19,79 +19,37 @@ import torch  # noqa: E402
 
 def build_sources():
     """Return {kernel_name: source} for the bench --gws stage kernels,
-    built exactly as DeviceFriedmannLoop would build them."""
+    built as DeviceFriedmannLoop builds them (stage 1, source only)."""
     import pystella_amd as ps
-    from pystella_amd.fusion import StencilRKStepper
+    from pystella_amd.fusion import DeviceFriedmannLoop, StencilRKStepper
     from pystella_amd.sectors import get_rho_and_p
-    import pystella_amd.backend.hip as hip
 
-    # stub out compilation: capture sources instead
-    captured = {}
+    grid = (512, 512, 512)
+    h = 2
+    dx = tuple(5 / n for n in grid)
+    dt = 1e-3
+    decomp = ps.DomainDecomposition((1, 1, 1), h, grid_shape=grid)
+    rank_shape = decomp.rank_shape
 
-    class _StubExt:
-        def jit_compile(self, src, name):
-            captured[name] = src
-            return name
+    def potential(f):
+        return (1.2e-6**2 / 2 * f[0]**2
+                + 2.5e-7 / 2 * f[0]**2 * f[1]**2) / 1.2e-6**2
 
-        def jit_launch(self, *a, **k):
-            raise RuntimeError("launch not available here")
+    sector = ps.ScalarSector(2, potential=potential)
+    sectors = [sector, ps.TensorPerturbationSector([sector])]
+    derivs = ps.FiniteDifferencer(decomp, h, dx, rank_shape=rank_shape)
+    stepper = StencilRKStepper(
+        ps.LowStorageRK54, sectors, derivs, halo_shape=h,
+        rank_shape=rank_shape, dt=dt, reducers=sector,
+        grid_size=float(np.prod(grid)), callback=get_rho_and_p,
+        inline_grad=True)
 
-    orig_ext = hip.ext
-    hip.ext = lambda: _StubExt()
-    try:
-        grid = (512, 512, 512)
-        h = 2
-        dx = tuple(5 / n for n in grid)
-        dt = 1e-3
-        decomp = ps.DomainDecomposition((1, 1, 1), h, grid_shape=grid)
-        rank_shape = decomp.rank_shape
-
-        def potential(f):
-            return (1.2e-6**2 / 2 * f[0]**2
-                    + 2.5e-7 / 2 * f[0]**2 * f[1]**2) / 1.2e-6**2
-
-        sector = ps.ScalarSector(2, potential=potential)
-        sectors = [sector, ps.TensorPerturbationSector([sector])]
-        derivs = ps.FiniteDifferencer(decomp, h, dx, rank_shape=rank_shape)
-        stepper = StencilRKStepper(
-            ps.LowStorageRK54, sectors, derivs, halo_shape=h,
-            rank_shape=rank_shape, dt=dt, reducers=sector,
-            grid_size=float(np.prod(grid)), callback=get_rho_and_p,
-            inline_grad=True)
-
-        smap = stepper._stepper.steps[1]
-        pad = tuple(n + 2 * h for n in rank_shape)
-        env = {
-            "f": torch.zeros((2,) + pad), "f_next": torch.zeros((2,) + pad),
-            "dfdt": torch.zeros((2,) + pad),
-            "f_tmp": torch.zeros((2,) + pad),
-            "dfdt_tmp": torch.zeros((2,) + pad),
-            "hij": torch.zeros((6,) + pad),
-            "hij_next": torch.zeros((6,) + pad),
-            "dhijdt": torch.zeros((6,) + pad),
-            "hij_tmp": torch.zeros((6,) + pad),
-            "dhijdt_tmp": torch.zeros((6,) + pad),
-            "a": np.ones(1), "hubble": np.zeros(1), "dt": dt,
-        }
-        if not stepper._stepper.tmp_arrays:
-            stepper._stepper.tmp_arrays = \
-                stepper._stepper.get_tmp_arrays_like(**env)
-        env.update(stepper._stepper.tmp_arrays)
-
-        m = smap._map
-        rs = m._infer_rank_shape(env)
-        from pystella_amd.backend.hip import get_lap_stage_kernel
-        for (rk_o, tmp_o, red_o, f_name, nf), fargs in zip(
-                smap.ring, smap._ring_field_args):
-            get_lap_stage_kernel(
-                rk_o, tmp_o, red_o or [(0.0, "sum")], fargs, [],
-                m.halo_shape, rs, smap.derivs.dx, nf,
-                f_name=f_name, lap_name=f"lap_{f_name}",
-                name=f"stage1_{f_name}",
-                state_map={"a": 0, "hubble": 4})
-    finally:
-        hip.ext = orig_ext
-    return captured
+    smap = stepper._stepper.steps[1]
+    kerns = smap.ring_kernels(rank_shape, torch.float64,
+                              state_map=DeviceFriedmannLoop.STATE_MAP,
+                              compile=False)
+    return {f"{smap._map.name}_{fam.f_name}": kern.source
+            for fam, kern in zip(smap.ring, kerns)}
 
 
 def compile_one(name, src, keep=None):
@@ -129,7 +87,9 @@ def main():
     p = ap.parse_args()
 
     srcs = build_sources()
-    print("kernels built:", sorted(srcs))
+    # the kernels carry the stepper's own names (rk_stage_red1_*; this
+    # tool used to rename them stage1_*)
+    print("kernels built, under the stepper's names:", sorted(srcs))
     for name, src in sorted(srcs.items()):
         if p.dump:
             os.makedirs(p.dump, exist_ok=True)

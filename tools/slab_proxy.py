@@ -1,7 +1,6 @@
 """Single-GPU proxy for the N=8 rank-local COMPUTE geometry: force the
 interior + 6-boundary-slab region split (as a (2,2,2) rank runs it)
-on one GPU at 256^3 and time the device loop.  A/B's the tile-matched
-slab kernel variants (PYSTELLA_SLAB_TILES=0/1).
+on one GPU at 256^3 and time the device loop.
 """
 
 import argparse
