@@ -303,6 +303,10 @@ class JitStencil:
                 elif x.index:
                     return
             elif isinstance(x, Field):
+                if x.shape:
+                    # the aggregate of a subscript seen above, not a
+                    # read of component 0
+                    return
                 f = x
             if f is None or f.name not in padded or not f.is_spatial:
                 return
@@ -838,11 +842,19 @@ _HIST_LDS_DOUBLES = 8192
 
 
 class JitHistogram:
+    """Simultaneous weighted histograms of fp64 or fp32 fields (``using
+    real = double|float``).  Bin values and weights are evaluated in
+    the fields' type; each weight is widened to double where it is
+    added, and the bins stay float64 whatever the fields are.
+    ``compile=False`` only generates ``self.source``."""
+
     def __init__(self, pairs, num_bins, field_args, scalar_names, halo,
-                 rank_shape, name="hist_map"):
+                 rank_shape, name="hist_map", dtype=None, compile=True):
+        dtype = dtype if dtype is not None else torch.float64
         self.rank_shape = tuple(rank_shape)
         self.num_bins = num_bins
         self.nhist = len(pairs)
+        self.dtype = dtype
         self.field_args = [fa for fa in field_args if fa.spatial]
         cg = Codegen(field_args, halo, rank_shape)
         body = []
@@ -855,7 +867,7 @@ class JitHistogram:
                 "atomicAdd(&lh[%d * NBINS + bb], (double)(%s)); }"
                 % (b, hh, w))
         ptr_params = ", ".join(
-            f"const double* __restrict__ {fa.name}"
+            f"const real* __restrict__ {fa.name}"
             for fa in self.field_args)
         dbl_params = ", ".join(f"double {c}" for c, _ in cg.scalars)
         params = ", ".join(x for x in (
@@ -864,20 +876,30 @@ class JitHistogram:
                     if self.nhist * num_bins <= _HIST_LDS_DOUBLES
                     else HISTOGRAM_GLOBAL_TEMPLATE)
         src = template.format(
-            defines=geometry_defines(halo, rank_shape), preamble=PREAMBLE,
+            defines=geometry_defines(halo, rank_shape,
+                                     rtype=_RTYPE[dtype]),
+            preamble=PREAMBLE,
             nhist=self.nhist, nbins=num_bins, name=name, params=params,
             body="\n        ".join(body))
         self.source = src
         self.scalar_keys = [k for _, k in cg.scalars]
-        self.key = ext().jit_compile(src, name)
+        # compile=False: source only (inspectable without a device)
+        self.key = ext().jit_compile(src, name) if compile else None
         total = int(np.prod(rank_shape))
         self.grid = min((total + 255) // 256, 1024)
 
     def __call__(self, env):
+        if self.key is None:
+            raise RuntimeError(
+                "JitHistogram was built with compile=False (source only)")
         ptrs = []
         dev = None
         for fa in self.field_args:
             t = _check_tensor(fa.name, env[fa.name])
+            if t.dtype != self.dtype:
+                raise TypeError(
+                    f"histogram argument '{fa.name}' has dtype "
+                    f"{t.dtype}, kernel compiled for {self.dtype}")
             dev = t.device
             ptrs.append(t.data_ptr())
         hist = torch.zeros((self.nhist, self.num_bins),
@@ -889,9 +911,9 @@ class JitHistogram:
 
 
 def get_histogram_kernel(pairs, num_bins, field_args, scalar_names, halo,
-                         rank_shape):
+                         rank_shape, dtype=None):
     return JitHistogram(pairs, num_bins, field_args, scalar_names, halo,
-                        rank_shape)
+                        rank_shape, dtype=dtype)
 
 
 # ---------------------------------------------------------------------------
@@ -904,7 +926,7 @@ SPECTRA_BIN_SRC = """
 #define NBINS {nbins}
 extern "C" __global__ __launch_bounds__(256) void spectra_bin(
     const double* __restrict__ fk, const double* __restrict__ wbase,
-    const int* __restrict__ bidx, double* __restrict__ hist, long n)
+    const int* __restrict__ bidx, double* __restrict__ hist, int n)
 {{
     __shared__ double lh[NBINS];
     for (int b = threadIdx.x; b < NBINS; b += 256) lh[b] = 0.0;

@@ -20,6 +20,7 @@
 
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -192,6 +193,13 @@ static void jit_launch(const std::string &key, int gx, int gy, int gz,
     auto it = g_kernels.find(key);
     if (it == g_kernels.end())
         throw std::runtime_error("unknown JIT kernel " + key);
+    // every integer parameter of a JIT kernel is declared ``int``
+    for (int64_t v : ints)
+        if (v < std::numeric_limits<int>::min() ||
+            v > std::numeric_limits<int>::max())
+            throw std::overflow_error(
+                "jit_launch: integer argument " + std::to_string(v) +
+                " of kernel " + key + " does not fit in int");
 
     struct Slot { alignas(16) unsigned char data[16]; };
     std::vector<Slot> storage(ptrs.size() + ints.size() + doubles.size());

@@ -211,20 +211,23 @@ class Projector:
             hij, hij_TT = queue, hij
             queue = None
         out = hij if hij_TT is None else hij_TT
-        if (isinstance(hij, torch.Tensor) and hij.is_cuda
-                and hij.dtype == torch.complex128
-                and hij.is_contiguous() and out.is_contiguous()):
+        if (self._gpu_fast(hij, out)
+                and tuple(hij.shape[:-3]) == (6,)
+                and tuple(out.shape[:-3]) == (6,)):
             from pystella_amd.backend.hip import _stream, ext
-            kshape = hij.shape[-3:]
+            kshape = self._kshape
             vol = int(np.prod(kshape))
-            kx = self.eff_mom["eff_mom_x"].contiguous()
-            ky = self.eff_mom["eff_mom_y"].contiguous()
-            kz = self.eff_mom["eff_mom_z"].contiguous()
+            kx, ky, kz = self._eff_c
             ext().tt_project(hij.data_ptr(), out.data_ptr(),
                              kx.data_ptr(), ky.data_ptr(), kz.data_ptr(),
                              int(kshape[1]), int(kshape[2]), vol,
                              _stream())
             return out
+        if (isinstance(hij, torch.Tensor) and isinstance(out, torch.Tensor)
+                and hij.device != out.device):
+            # copy_ below would move the result across devices silently
+            raise ValueError(
+                f"hij is on {hij.device} but hij_TT is on {out.device}")
         khat = self.khat
 
         def P(a, b):

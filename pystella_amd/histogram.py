@@ -5,7 +5,9 @@ hand-written CDNA4 kernel: per-workgroup LDS bin accumulation with LDS
 atomics, merged with device-scope atomics into the global histogram —
 two launches (zero + accumulate) instead of the reference's in-kernel
 global barrier (histogram.py:129).  Bin/weight expressions are spliced
-in via hiprtc.  CPU path: torch ``index_add_`` (oracle).
+in via hiprtc; the kernel is built for the fields' dtype (float64 or
+float32) and always bins in float64.  CPU path: torch ``index_add_``
+(oracle).
 """
 
 from __future__ import annotations
@@ -105,12 +107,21 @@ class Histogrammer:
 
     def _local_hip(self, env, rank_shape):
         from pystella_amd.backend.hip import get_histogram_kernel
+        dtype = None
+        for fa in self.field_args:
+            t = env.get(fa.name)
+            if isinstance(t, torch.Tensor) and fa.spatial:
+                dtype = t.dtype
+                break
+        if dtype is None:
+            dtype = torch.float64
         if self._hip_kernel is None or \
-                self._hip_kernel.rank_shape != rank_shape:
+                self._hip_kernel.rank_shape != rank_shape or \
+                self._hip_kernel.dtype != dtype:
             self._hip_kernel = get_histogram_kernel(
                 list(self.histograms.values()), self.num_bins,
                 self.field_args, sorted(self.scalar_names),
-                self.halo_shape, rank_shape)
+                self.halo_shape, rank_shape, dtype=dtype)
         return self._hip_kernel(env)
 
     def __call__(self, queue=None, filter_args=False, **kwargs):
