@@ -53,6 +53,10 @@ parser.add_argument("--no-output", action="store_true")
 # (see tools/reference_crosscheck.py)
 parser.add_argument("--save-init", default=None, metavar="FILE.npz")
 parser.add_argument("--load-init", default=None, metavar="FILE.npz")
+# "torch": per-rank generators, the realization depends on --proc-shape;
+# "philox": counter-based on the global mode index, one seed on every
+# rank, the same realization on any --proc-shape and device count
+parser.add_argument("--rng", default="torch", choices=["torch", "philox"])
 
 
 def main(args=None):
@@ -223,8 +227,12 @@ def main(args=None):
         float(eval_expr(x, {"f0": np.array(f0)}, ctx)) + hubble_correction
         for x in d2Vd2f]
 
-    modes = ps.RayleighGenerator(fft=fft, dk=dk, volume=volume,
-                                 seed=49279 * (decomp.rank + 1))
+    if p.rng == "philox":
+        modes = ps.RayleighGenerator(fft=fft, dk=dk, volume=volume,
+                                     seed=49279, rng="philox")
+    else:
+        modes = ps.RayleighGenerator(fft=fft, dk=dk, volume=volume,
+                                     seed=49279 * (decomp.rank + 1))
     for fld in range(nscalars):
         modes.init_WKB_fields(
             f[fld], dfdt[fld], norm=p.mphi**2,

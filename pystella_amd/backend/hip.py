@@ -1384,6 +1384,241 @@ def kspace_poisson(rhok, sol, ex, ey, ez, inv_n, m_squared):
 
 
 # ---------------------------------------------------------------------------
+# fused Rayleigh mode kernel (RayleighGenerator rng="philox", closes K12):
+# from the Philox4x32-10 words to the stored mode in one launch, one
+# thread per mode, no k-space temporaries.  The definition is
+# fourier/philox.py's; the counter holds the *global* canonical mode
+# index, so a thread draws its Hermitian partner's numbers itself and
+# every layout stores the same realisation.  The ten rounds live in
+# named scalars (a runtime-indexed array would go to scratch) and the
+# high products are __umulhi.  sincospi(2u) needs no large-argument
+# reduction.  All arithmetic is double; the value is rounded once, on
+# its 16- or 8-byte store.
+
+RAYLEIGH_KERNEL = """
+typedef unsigned int u32;
+
+#define PHILOX_ROUND(K0, K1) {{ \\
+    const u32 hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0; \\
+    const u32 hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2; \\
+    c0 = hi1 ^ c1 ^ (K0); c1 = lo1; \\
+    c2 = hi0 ^ c3 ^ (K1); c3 = lo0; }}
+
+// z = amp * sqrt_power * exp(2 pi i u_phs) of counter (c0, c1, c2, c3)
+__device__ inline double2 rayleigh_mode(u32 c0, u32 c1, u32 c2, u32 c3,
+                                        const u32 k0, const u32 k1,
+                                        const double sp)
+{{
+    PHILOX_ROUND(k0, k1)
+    PHILOX_ROUND(k0 + 0x9E3779B9u, k1 + 0xBB67AE85u)
+    PHILOX_ROUND(k0 + 0x3C6EF372u, k1 + 0x76CF5D0Au)
+    PHILOX_ROUND(k0 + 0xDAA66D2Bu, k1 + 0x32370B8Fu)
+    PHILOX_ROUND(k0 + 0x78DDE6E4u, k1 + 0xED9EBA14u)
+    PHILOX_ROUND(k0 + 0x1715609Du, k1 + 0xA9066899u)
+    PHILOX_ROUND(k0 + 0xB54CDA56u, k1 + 0x646E171Eu)
+    PHILOX_ROUND(k0 + 0x5384540Fu, k1 + 0x1FD5C5A3u)
+    PHILOX_ROUND(k0 + 0xF1BBCDC8u, k1 + 0xDB3D7428u)
+    PHILOX_ROUND(k0 + 0x8FF34781u, k1 + 0x96A522ADu)
+    // exact doubles in (0, 1]
+    const double u_phs = (double)((((unsigned long long)(c2 >> 11) << 32)
+                                   | c3) + 1ull) * 0x1p-53;
+#if RANDOM
+    const double u_amp = (double)((((unsigned long long)(c0 >> 11) << 32)
+                                   | c1) + 1ull) * 0x1p-53;
+    const double a = sqrt(-log(u_amp)) * sp;
+#else
+    const double a = sp;
+#endif
+    double s, c;
+    sincospi(2.0 * u_phs, &s, &c);
+    return make_double2(a * c, a * s);
+}}
+
+extern "C" __global__ __launch_bounds__(256) void {name}(
+    {params})
+{{
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= VOLK) return;
+    const int kk = (int)(idx % NKZ);
+    const int jj = (int)((idx / NKZ) % NKY);
+    const int ii = (int)(idx / ((long)NKZ * NKY));
+    const int gx = gxs[ii], gy = gys[jj], gz = gzs[kk];
+    int cx = gx, cy = gy;
+    bool conj = false, self = false;
+#if IS_REAL
+    if (gz == 0 || (NZ % 2 == 0 && gz == NZ / 2)) {{
+        const int px = (NX - gx) % NX, py = (NY - gy) % NY;
+        self = (px == gx) && (py == gy);
+        if (!(gx < px || (gx == px && gy <= py))) {{
+            cx = px; cy = py; conj = true;
+        }}
+    }}
+#endif
+    const u32 k0 = (u32)seed_lo, k1 = (u32)seed_hi;
+    const double sp = sqrt_power[idx];
+    {body}
+}}
+"""
+
+_RAYLEIGH_STORE = """{{
+        const double im = self ? 0.0 : (conj ? -{v}.y : {v}.y);
+        {out}[idx] = make_{ct}(({rt}){v}.x, ({rt})im);
+    }}"""
+
+_RAYLEIGH_CTYPES = {torch.complex128: ("double2", "double"),
+                    torch.complex64: ("float2", "float"),
+                    "complex128": ("double2", "double"),
+                    "complex64": ("float2", "float")}
+
+
+def rayleigh_source(kshape, grid_shape, *, wkb, is_real, random, ctype):
+    """HIP source of the fused Rayleigh mode kernel over this rank's
+    k-space ``kshape`` of the global ``grid_shape``.  ``wkb`` selects the
+    (f_k, f'_k) pair, ``is_real`` the Hermitian planes of an r2c
+    transform, ``random`` the Rayleigh amplitude (else 1), ``ctype``
+    (``torch.complex128``/``complex64`` or their names) the stored
+    type.  Needs no device."""
+    try:
+        ct, rt = _RAYLEIGH_CTYPES[ctype]
+    except (KeyError, TypeError):
+        raise ValueError(f"ctype must be complex128 or complex64, "
+                         f"got {ctype!r}") from None
+    if len(kshape) != 3 or len(grid_shape) != 3:
+        raise ValueError("kshape and grid_shape are 3-tuples")
+    wkb, is_real, random = bool(wkb), bool(is_real), bool(random)
+    params = [f"{ct}* __restrict__ fk"]
+    if wkb:
+        params.append(f"{ct}* __restrict__ dfk")
+    params.append("const double* __restrict__ sqrt_power")
+    if wkb:
+        params.append("const double* __restrict__ omega")
+    params += [f"const int* __restrict__ {t}" for t in ("gxs", "gys", "gzs")]
+    params += ["const int seed_lo", "const int seed_hi", "const int draw"]
+    if wkb:
+        params.append("const double hubble")
+    mode = ("rayleigh_mode((u32)cx, (u32)cy, (u32)gz, 2u * (u32)draw + %du, "
+            "k0, k1, sp)")
+    if wkb:
+        body = [
+            f"const double2 L = {mode % 0};",
+            f"const double2 R = {mode % 1};",
+            "const double rs2 = 0.70710678118654752440;",
+            "const double2 f = make_double2((L.x + R.x) * rs2, "
+            "(L.y + R.y) * rs2);",
+            "const double2 d = make_double2((L.x - R.x) * rs2, "
+            "(L.y - R.y) * rs2);",
+            "const double w = omega[idx];",
+            "const double2 g = make_double2(-(w * d.y) - hubble * f.x, "
+            "w * d.x - hubble * f.y);",
+            _RAYLEIGH_STORE.format(v="f", out="fk", ct=ct, rt=rt),
+            _RAYLEIGH_STORE.format(v="g", out="dfk", ct=ct, rt=rt)]
+    else:
+        body = [f"const double2 z = {mode % 0};",
+                _RAYLEIGH_STORE.format(v="z", out="fk", ct=ct, rt=rt)]
+    head = "".join(
+        f"#define {n} {int(v)}\n" for n, v in zip(
+            ("NKX", "NKY", "NKZ", "NX", "NY", "NZ", "WKB", "IS_REAL",
+             "RANDOM"),
+            tuple(kshape) + tuple(grid_shape) + (wkb, is_real, random)))
+    head += (f"#define CTYPE {ct}\n"
+             "#define VOLK ((long)NKX * NKY * NKZ)\n")
+    return head + RAYLEIGH_KERNEL.format(
+        name="rayleigh_modes", params=",\n    ".join(params),
+        body="\n    ".join(body))
+
+
+_rayleigh_cache = {}
+
+
+def _rayleigh_real(name, t, kshape):
+    _check_tensor(name, t)
+    if t.dtype != torch.float64:
+        raise TypeError(f"argument {name} has dtype {t.dtype}; the "
+                        "Rayleigh kernel reads float64")
+    if tuple(t.shape) != kshape:
+        raise ValueError(f"argument {name} has shape {tuple(t.shape)}, "
+                         f"expected {kshape}")
+
+
+def rayleigh_modes(fk, dfk, sqrt_power, omega, tables, grid_shape, seed,
+                   draw, hubble=0., *, is_real, random=True):
+    """One launch: fill ``fk`` (and, for the WKB pair, ``dfk``) with the
+    modes that fourier/philox.py defines for ``(seed, draw)``.
+
+    :arg fk, dfk: contiguous complex128 or complex64 device tensors of
+        this rank's k-shape; ``dfk=None`` selects ``generate``, and then
+        ``omega`` is None as well.
+    :arg sqrt_power, omega: float64 device tensors of the same shape.
+    :arg tables: three flat int32 device tensors, this rank's global
+        mode indices along each axis.
+    """
+    from pystella_amd.fourier.philox import check_draw, check_seed
+    wkb = dfk is not None
+    _check_tensor("fk", fk)
+    if fk.dtype not in (torch.complex128, torch.complex64):
+        raise TypeError(f"argument fk has dtype {fk.dtype}; the Rayleigh "
+                        "kernel stores complex128 or complex64")
+    if fk.dim() != 3:
+        raise ValueError(f"argument fk has shape {tuple(fk.shape)}, "
+                         "expected a 3-D k-space array")
+    kshape = tuple(fk.shape)
+    if wkb:
+        _check_tensor("dfk", dfk)
+        if dfk.dtype != fk.dtype:
+            raise TypeError(f"argument dfk has dtype {dfk.dtype}, fk has "
+                            f"{fk.dtype}")
+        if tuple(dfk.shape) != kshape:
+            raise ValueError(f"argument dfk has shape {tuple(dfk.shape)}, "
+                             f"expected {kshape}")
+        if dfk.data_ptr() == fk.data_ptr() and fk.numel():
+            raise ValueError("output dfk aliases fk")
+    if (omega is not None) != wkb:
+        raise ValueError("omega goes with dfk: pass both or neither")
+    _rayleigh_real("sqrt_power", sqrt_power, kshape)
+    if wkb:
+        _rayleigh_real("omega", omega, kshape)
+    if len(tables) != 3 or len(grid_shape) != 3:
+        raise ValueError("tables and grid_shape have three entries")
+    for ax, t, n in zip("xyz", tables, kshape):
+        _check_tensor(f"tables[{ax}]", t)
+        if t.dtype != torch.int32:
+            raise TypeError(f"argument tables[{ax}] has dtype {t.dtype}; "
+                            "the index tables are int32")
+        if t.dim() != 1 or t.numel() != n:
+            raise ValueError(f"argument tables[{ax}] has shape "
+                             f"{tuple(t.shape)}, expected ({n},)")
+    grid_shape = tuple(int(n) for n in grid_shape)
+    if min(grid_shape) < 1 or max(grid_shape) >= 2**31:
+        raise ValueError(f"grid_shape {grid_shape} is out of range")
+    seed = check_seed(seed)
+    draw = check_draw(draw)
+    vol = int(np.prod(kshape))
+    if vol == 0:
+        return
+    flags = dict(wkb=wkb, is_real=bool(is_real), random=bool(random),
+                 ctype=fk.dtype)
+    key = (kshape, grid_shape) + tuple(sorted(flags.items(),
+                                              key=lambda kv: kv[0]))
+    kid = _rayleigh_cache.get(key)
+    if kid is None:
+        kid = ext().jit_compile(
+            rayleigh_source(kshape, grid_shape, **flags), "rayleigh_modes")
+        _rayleigh_cache[key] = kid
+
+    def signed(w):
+        return w - 2**32 if w >= 2**31 else w
+
+    ptrs = [fk.data_ptr()] + ([dfk.data_ptr()] if wkb else [])
+    ptrs.append(sqrt_power.data_ptr())
+    if wkb:
+        ptrs.append(omega.data_ptr())
+    ptrs += [t.data_ptr() for t in tables]
+    ext().jit_launch(kid, (vol + 255) // 256, 1, 1, 256, 1, 1, 0, _stream(),
+                     ptrs, [signed(seed & 0xffffffff), signed(seed >> 32),
+                            draw], [float(hubble)] if wkb else [])
+
+
+# ---------------------------------------------------------------------------
 # AOT stencil kernels (csrc/derivs.hip)
 
 def _flat_fields(t, ndim_grid=3):

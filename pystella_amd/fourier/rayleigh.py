@@ -3,14 +3,19 @@
 Analogue of reference pystella/fourier/rayleigh.py:35-395.  Mode
 amplitudes are Rayleigh-distributed (amp = √(−ln u₀)) with uniform
 phases; the WKB variant initializes (f, ḟ) pairs for Klein-Gordon
-fields in conformal FLRW.  Random numbers come from torch's
-counter-based Philox generator (per-rank seeds), replacing
-pyopencl.clrandom Threefry (reference rayleigh.py:154).
+fields in conformal FLRW.  By default (``rng="torch"``) random numbers
+come from torch's counter-based Philox generator (per-rank seeds),
+replacing pyopencl.clrandom Threefry (reference rayleigh.py:154).
 
 For real fields the kz=0 and kz=Nyquist planes are made exactly
 Hermitian-symmetric (vectorized analogue of reference
 ``make_hermitian``, rayleigh.py:35-55) and corner-mode imaginary parts
 are zeroed, so c2r transforms see consistent data.
+
+With ``rng="philox"`` the modes are those of fourier/philox.py instead:
+Philox4x32-10 keyed on the global mode index, one fused HIP kernel on
+the GPU (backend/hip.py ``rayleigh_modes``), Hermitian planes included
+on every layout.
 """
 
 from __future__ import annotations
@@ -48,14 +53,32 @@ class RayleighGenerator:
     :arg fft: an FFT object from :func:`~pystella_amd.DFT`.
     :arg dk: 3-tuple momentum-space spacing.
     :arg volume: physical box volume.
-    :arg seed: RNG seed (make it rank-dependent for distributed runs,
-        as the reference example does: scalar_preheating.py:227).
+    :arg seed: RNG seed.  With ``rng="torch"`` make it rank-dependent
+        for distributed runs, as the reference example does
+        (scalar_preheating.py:227); with ``rng="philox"`` it is an
+        integer in [0, 2**64) and every rank passes the same one.
+    :arg rng: ``"torch"`` (the default) draws from a per-rank
+        ``torch.Generator``: a realisation depends on the layout, and
+        on pencil layouts the kz = 0 and Nyquist planes are not made
+        Hermitian.  ``"philox"`` keys a counter-based generator on the
+        global mode index (fourier/philox.py; one fused HIP kernel on
+        the GPU): the same seed gives the same, exactly Hermitian,
+        realisation on every layout and device count.  The two
+        generators give different realisations for the same seed.
+
+    With ``rng="philox"`` the integer attribute ``draw`` (readable and
+    settable, initially 0, below 2**30) numbers the realisations of one
+    seed: each :meth:`generate` or :meth:`generate_WKB` call uses the
+    current ``draw`` and then increments it.
     """
 
     def __init__(self, context_or_fft=None, fft=None, dk=None, volume=None,
-                 seed=13298):
+                 seed=13298, rng="torch"):
         if fft is None:
             fft = context_or_fft
+        if rng not in ("torch", "philox"):
+            raise ValueError(f"rng must be 'torch' or 'philox', got {rng!r}")
+        self.rng = rng
         self.fft = fft
         self.volume = volume
         dev = fft.fk.device
@@ -67,9 +90,16 @@ class RayleighGenerator:
         self.kmags = np.sqrt(sum((dki * ki)**2
                                  for dki, ki in zip(dk, kvecs)))
         self._kmags_t = torch.as_tensor(self.kmags, device=dev)
+        self.cdtype = fft.fk.dtype
+        if rng == "philox":
+            from pystella_amd.fourier import philox
+            self.seed = philox.check_seed(seed)
+            self.draw = 0
+            self._gidx = philox.global_indices(fft)
+            self._gidx_t = None
+            return
         self.gen = torch.Generator(device=dev)
         self.gen.manual_seed(int(seed))
-        self.cdtype = fft.fk.dtype
 
     # ------------------------------------------------------------------
     def _window_sq(self, window):
@@ -147,12 +177,61 @@ class RayleighGenerator:
         return torch.as_tensor(power, device=self.device)
 
     # ------------------------------------------------------------------
+    # rng="philox": sqrt_power (and omega) are the only k-space inputs;
+    # one launch writes freshly allocated outputs, Hermitian planes and
+    # self-conjugate modes included (no make_hermitian, no
+    # zero_corner_modes)
+
+    def _sqrt_power(self, amplitude_sq, window, power):
+        """sqrt(amplitude_sq * window**2 * power), in ``power``'s storage
+        (a fresh array of :meth:`_ps_wrapper`)."""
+        power *= self._window_sq(window)
+        power *= amplitude_sq
+        return power.sqrt_()
+
+    def _philox_modes(self, random, sqrt_power, omega=None, hubble=0.):
+        from pystella_amd.fourier import philox
+        draw = philox.check_draw(self.draw)
+        wkb = omega is not None
+        grid_shape = tuple(self.fft.grid_shape)
+        is_real = bool(self.fft.is_real)
+        if self.device.type == "cuda":
+            from pystella_amd.backend import hip
+            if self._gidx_t is None:
+                self._gidx_t = [
+                    torch.as_tensor(g.astype(np.int32), device=self.device)
+                    for g in self._gidx]
+            shape = tuple(sqrt_power.shape)
+            fk = torch.empty(shape, dtype=self.cdtype, device=self.device)
+            dfk = torch.empty_like(fk) if wkb else None
+            hip.rayleigh_modes(fk, dfk, sqrt_power, omega, self._gidx_t,
+                               grid_shape, self.seed, draw, hubble,
+                               is_real=is_real, random=random)
+            out = (fk, dfk) if wkb else fk
+        elif wkb:
+            out = tuple(
+                torch.as_tensor(a).to(self.cdtype)
+                for a in philox.modes_WKB(
+                    self.seed, draw, self._gidx, grid_shape, is_real,
+                    sqrt_power.numpy(), omega.numpy(), hubble, random))
+        else:
+            out = torch.as_tensor(philox.modes(
+                self.seed, draw, self._gidx, grid_shape, is_real,
+                sqrt_power.numpy(), random)).to(self.cdtype)
+        self.draw = draw + 1
+        return out
+
+    # ------------------------------------------------------------------
     def generate(self, queue=None, random=True,
                  field_ps=lambda kmag: 1 / 2 / kmag, norm=1,
                  window=lambda kmag: 1.):
         """Generate Fourier modes with power spectrum ``field_ps``
         (reference rayleigh.py:185-227)."""
         amplitude_sq = norm / self.volume
+        if self.rng == "philox":
+            return self._philox_modes(random, self._sqrt_power(
+                amplitude_sq, window,
+                self._ps_wrapper(field_ps, self._kmags_t, self.kmags)))
         rands = self._uniform(2)
         if not random:
             rands[0] = np.exp(-1.)
@@ -174,6 +253,15 @@ class RayleighGenerator:
         """Generate (f_k, ḟ_k) pairs via the WKB approximation
         (reference rayleigh.py:325-373)."""
         amplitude_sq = norm / self.volume
+        if self.rng == "philox":
+            omega = torch.as_tensor(
+                np.asarray(omega_k(self.kmags), dtype=np.float64)
+                * np.ones_like(self.kmags), device=self.device)
+            return self._philox_modes(
+                random, self._sqrt_power(
+                    amplitude_sq, window,
+                    self._ps_wrapper(field_ps, omega, self.kmags)),
+                omega, hubble)
         rands = self._uniform(4)
         if not random:
             rands[0] = rands[2] = np.exp(-1.)
