@@ -924,8 +924,8 @@ def get_histogram_kernel(pairs, num_bins, field_args, scalar_names, halo,
 
 SPECTRA_BIN_SRC = """
 #define NBINS {nbins}
-extern "C" __global__ __launch_bounds__(256) void spectra_bin(
-    const double* __restrict__ fk, const double* __restrict__ wbase,
+extern "C" __global__ __launch_bounds__(256) void {name}(
+    const {fk_t}* __restrict__ fk, const double* __restrict__ wbase,
     const int* __restrict__ bidx, double* __restrict__ hist, int n)
 {{
     __shared__ double lh[NBINS];
@@ -934,8 +934,7 @@ extern "C" __global__ __launch_bounds__(256) void spectra_bin(
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long stride = (long)gridDim.x * blockDim.x;
     for (; i < n; i += stride) {{
-        const double re = fk[2 * i];
-        const double im = fk[2 * i + 1];
+        {load}
         atomicAdd(&lh[bidx[i]], wbase[i] * (re * re + im * im));
     }}
     __syncthreads();
@@ -944,19 +943,62 @@ extern "C" __global__ __launch_bounds__(256) void spectra_bin(
 }}
 """
 
+# storage type -> (kernel name, fk element type, the load of one mode).
+# A complex64 mode moves as one 8-byte access and is widened on load;
+# |f|^2, the weights and the bins are double for either storage type.
+_SPECTRA_BIN_FORMS = {
+    "complex128": ("spectra_bin", "double",
+                   "const double re = fk[2 * i];\n"
+                   "        const double im = fk[2 * i + 1];"),
+    "complex64": ("spectra_bin_c64", "float2",
+                  "const float2 v = fk[i];\n"
+                  "        const double re = (double)v.x;\n"
+                  "        const double im = (double)v.y;"),
+}
+_CTYPE_NAMES = {torch.complex128: "complex128", torch.complex64: "complex64",
+                "complex128": "complex128", "complex64": "complex64"}
+
+
+def _ctype_name(ctype):
+    try:
+        return _CTYPE_NAMES[ctype]
+    except (KeyError, TypeError):
+        raise ValueError(f"ctype must be complex128 or complex64, "
+                         f"got {ctype!r}") from None
+
+
+def spectra_bin_source(num_bins, ctype="complex128"):
+    """HIP source of the binning kernel for ``num_bins`` bins and modes
+    stored as ``ctype``.  Needs no device."""
+    name, fk_t, load = _SPECTRA_BIN_FORMS[_ctype_name(ctype)]
+    return SPECTRA_BIN_SRC.format(nbins=int(num_bins), name=name, fk_t=fk_t,
+                                  load=load)
+
+
 _spectra_bin_cache = {}
 
 
-def spectra_bin(fk, wbase, bidx, num_bins):
-    """|f_k|²-weighted LDS-binned histogram; fk complex128, wbase fp64,
-    bidx int32 (all flat, same length).  Returns fp64 hist[num_bins]."""
+def _spectra_bin(fk, wbase, bidx, num_bins, ctype):
     _check_tensor("fk", fk)
+    if fk.dtype != getattr(torch, ctype):
+        raise TypeError(f"argument fk has dtype {fk.dtype}; this binning "
+                        f"kernel takes {ctype}")
     n = fk.numel()
-    key = num_bins
+    for name, t, dtype in (("wbase", wbase, torch.float64),
+                           ("bidx", bidx, torch.int32)):
+        _check_tensor(name, t)
+        if t.dtype != dtype:
+            raise TypeError(f"argument {name} has dtype {t.dtype}, "
+                            f"expected {dtype}")
+        if t.numel() != n:
+            raise ValueError(f"argument {name} has {t.numel()} elements, "
+                             f"fk has {n}")
+    # the complex128 key is the bare bin count, as it always was
+    key = num_bins if ctype == "complex128" else (num_bins, ctype)
     k = _spectra_bin_cache.get(key)
     if k is None:
-        src = SPECTRA_BIN_SRC.format(nbins=num_bins)
-        kid = ext().jit_compile(src, "spectra_bin")
+        src = spectra_bin_source(num_bins, ctype)
+        kid = ext().jit_compile(src, _SPECTRA_BIN_FORMS[ctype][0])
         _spectra_bin_cache[key] = k = kid
     hist = torch.zeros(num_bins, dtype=torch.float64, device=fk.device)
     grid = min(4096, (n + 255) // 256)
@@ -966,11 +1008,25 @@ def spectra_bin(fk, wbase, bidx, num_bins):
     return hist
 
 
+def spectra_bin(fk, wbase, bidx, num_bins):
+    """|f_k|²-weighted LDS-binned histogram; fk complex128, wbase fp64,
+    bidx int32 (all flat, same length).  Returns fp64 hist[num_bins]."""
+    return _spectra_bin(fk, wbase, bidx, num_bins, "complex128")
+
+
+def spectra_bin_c64(fk, wbase, bidx, num_bins):
+    """:func:`spectra_bin` for complex64 modes: one 8-byte load per mode,
+    widened once; the sum and ``hist`` are fp64 as there."""
+    return _spectra_bin(fk, wbase, bidx, num_bins, "complex64")
+
+
 # ---------------------------------------------------------------------------
 # fused k-space projector kernels: one launch per operation, ε-basis
 # built in registers (reference pystella/fourier/projectors.py:108-236
 # runs each of these as ONE generated kernel too; round 1 shipped them
-# as multi-launch torch chains — these close K10)
+# as multi-launch torch chains — these close K10).  The storage type of
+# the modes is a generation-time choice (complex128, or complex64 for the
+# objects built on a float32 transform); the bodies are the same.
 
 PROJECTOR_PREAMBLE = """
 struct cplx { double x; double y; };
@@ -981,11 +1037,27 @@ __device__ inline cplx cadd(cplx a, cplx b)
 __device__ inline cplx conjg(cplx a) { return {a.x, -a.y}; }
 __device__ inline cplx cscale(double s, cplx a)
 { return {s * a.x, s * a.y}; }
+%LDST%"""
+
+# how a mode is loaded and stored, per storage type (the %LDST% of
+# PROJECTOR_PREAMBLE) with the element type of the data pointers.
+# complex64 moves as one float2 access, widened once on the load and
+# rounded once on the store; cplx and all arithmetic stay double.
+_PROJECTOR_LDST = {
+    "complex128": ("double", """\
 #define LDC(p, c) cplx{ (p)[2*((long)(c)*VOLK + idx)], \\
                         (p)[2*((long)(c)*VOLK + idx) + 1] }
 #define STC(p, c, v) { (p)[2*((long)(c)*VOLK + idx)] = (v).x; \\
                        (p)[2*((long)(c)*VOLK + idx) + 1] = (v).y; }
-"""
+"""),
+    "complex64": ("float2", """\
+__device__ inline cplx widen(const float2 v)
+{ return {(double)v.x, (double)v.y}; }
+#define LDC(p, c) widen((p)[(long)(c)*VOLK + idx])
+#define STC(p, c, v) { (p)[(long)(c)*VOLK + idx] = \\
+                           make_float2((float)(v).x, (float)(v).y); }
+"""),
+}
 
 PROJECTOR_KERNEL = """
 extern "C" __global__ __launch_bounds__(256) void {name}(
@@ -1132,17 +1204,42 @@ _PROJ_BODIES = _projector_bodies()
 _proj_cache = {}
 
 
-def projector_source(op, kshape, times_abs_k=False):
+def _proj_kernel_name(op, ctype):
+    return f"proj_{op}" + ("_c64" if ctype == "complex64" else "")
+
+
+def projector_source(op, kshape, times_abs_k=False, ctype="complex128"):
+    """HIP source of projector kernel ``op``; ``ctype`` is the storage
+    type of every data pointer.  Needs no device."""
     body, names, needs_eps = _PROJ_BODIES[op]
-    params = ",\n    ".join(f"double* __restrict__ {n}" for n in names)
+    ctype = _ctype_name(ctype)
+    elem, ldst = _PROJECTOR_LDST[ctype]
+    params = ",\n    ".join(f"{elem}* __restrict__ {n}" for n in names)
     head = (f"#define TIMES_ABS_K {1 if times_abs_k else 0}\n"
             f"#define NKX {kshape[0]}\n"
             f"#define NKY {kshape[1]}\n"
             f"#define NKZ {kshape[2]}\n"
             "#define VOLK ((long)NKX * NKY * NKZ)\n")
-    return head + PROJECTOR_PREAMBLE + PROJECTOR_KERNEL.format(
-        name=f"proj_{op}", params=params,
-        eps=PROJECTOR_EPS if needs_eps else "", body=body)
+    return (head + PROJECTOR_PREAMBLE.replace("%LDST%", ldst)
+            + PROJECTOR_KERNEL.format(
+                name=_proj_kernel_name(op, ctype), params=params,
+                eps=PROJECTOR_EPS if needs_eps else "", body=body))
+
+
+def _projector_launch(op, kshape, ptrs, eff, times_abs_k, ctype):
+    # the complex128 key is the one it always was
+    key = (op, tuple(kshape), bool(times_abs_k))
+    if ctype != "complex128":
+        key += (ctype,)
+    kid = _proj_cache.get(key)
+    if kid is None:
+        src = projector_source(op, kshape, times_abs_k, ctype)
+        kid = ext().jit_compile(src, _proj_kernel_name(op, ctype))
+        _proj_cache[key] = kid
+    vol = int(np.prod(kshape))
+    grid = (vol + 255) // 256
+    ext().jit_launch(kid, grid, 1, 1, 256, 1, 1, 0, _stream(),
+                     list(ptrs) + [e.data_ptr() for e in eff], [], [])
 
 
 def projector_op(op, kshape, ptrs, eff, times_abs_k=False):
@@ -1151,17 +1248,73 @@ def projector_op(op, kshape, ptrs, eff, times_abs_k=False):
     :arg ptrs: list of data_ptrs in the op's parameter order.
     :arg eff: (eff_x, eff_y, eff_z) contiguous fp64 device tensors.
     """
-    body, names, needs_eps = _PROJ_BODIES[op]
-    key = (op, tuple(kshape), bool(times_abs_k))
-    kid = _proj_cache.get(key)
-    if kid is None:
-        src = projector_source(op, kshape, times_abs_k)
-        kid = ext().jit_compile(src, f"proj_{op}")
-        _proj_cache[key] = kid
+    _projector_launch(op, kshape, ptrs, eff, times_abs_k, "complex128")
+
+
+def _c64_tensor(name, t, shape):
+    _check_tensor(name, t)
+    if t.dtype != torch.complex64:
+        raise TypeError(f"argument {name} has dtype {t.dtype}; the "
+                        "complex64 observable kernels take complex64")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"argument {name} has shape {tuple(t.shape)}, "
+                         f"expected {tuple(shape)}")
+
+
+def _c64_tables(eff, kshape):
+    if len(eff) != 3:
+        raise ValueError("eff has three entries")
+    for ax, e, n in zip("xyz", eff, kshape):
+        _kspace_table(f"eff_{ax}", e, n)
+
+
+# leading component counts of each op's tensors, in parameter order
+_PROJ_LEADING = {
+    "transversify": (3, 3), "vec_to_pol": (3, 0, 0),
+    "pol_to_vec": (0, 0, 3), "decompose_vector": (3, 0, 0, 0),
+    "decomp_to_vec": (0, 0, 0, 3), "tensor_to_pol": (6, 0, 0),
+    "pol_to_tensor": (0, 0, 6)}
+
+
+def projector_op_c64(op, kshape, tensors, eff, times_abs_k=False):
+    """:func:`projector_op` for complex64 modes.  Takes the tensors
+    themselves, in the op's parameter order, and checks them: contiguous
+    complex64 device tensors of ``(ncomp,) + kshape`` (``kshape`` alone
+    for a scalar), outputs possibly views of the input as in
+    :func:`projector_op`.  ``eff`` stays fp64."""
+    if op not in _PROJ_LEADING:
+        raise ValueError(f"unknown projector op {op!r}")
+    kshape = tuple(int(n) for n in kshape)
+    lead = _PROJ_LEADING[op]
+    if len(tensors) != len(lead):
+        raise ValueError(f"{op} takes {len(lead)} tensors, "
+                         f"got {len(tensors)}")
+    for i, (t, nc) in enumerate(zip(tensors, lead)):
+        _c64_tensor(f"tensors[{i}]", t,
+                    ((nc,) if nc else ()) + kshape)
+    _c64_tables(eff, kshape)
+    if int(np.prod(kshape)) == 0:
+        return
+    _projector_launch(op, kshape, [t.data_ptr() for t in tensors], eff,
+                      times_abs_k, "complex64")
+
+
+def tt_project_c64(hij, out, eff, kshape):
+    """Transverse-traceless projection of a complex64 ``hij`` of shape
+    ``(6,) + kshape`` into ``out`` (which may be ``hij``) on the f64
+    matrix cores: 8-byte loads widened to double, one rounded 8-byte
+    store (csrc/tt_mfma.hip)."""
+    kshape = tuple(int(n) for n in kshape)
+    _c64_tensor("hij", hij, (6,) + kshape)
+    _c64_tensor("out", out, (6,) + kshape)
+    _c64_tables(eff, kshape)
     vol = int(np.prod(kshape))
-    grid = (vol + 255) // 256
-    ext().jit_launch(kid, grid, 1, 1, 256, 1, 1, 0, _stream(),
-                     list(ptrs) + [e.data_ptr() for e in eff], [], [])
+    if vol == 0:
+        return
+    ext().tt_project_c64(hij.data_ptr(), out.data_ptr(),
+                         eff[0].data_ptr(), eff[1].data_ptr(),
+                         eff[2].data_ptr(), kshape[1], kshape[2], vol,
+                         _stream())
 
 
 # ---------------------------------------------------------------------------

@@ -29,9 +29,14 @@ __device__ __forceinline__ int sym_idx(int a, int b)
     return a * 3 - (a * (a + 1)) / 2 + b;
 }
 
+// T is the storage type of one real part: double for complex128 modes,
+// float for complex64.  A mode moves as one 16- or 8-byte nontemporal
+// access; a float mode is widened once on its load and rounded once on
+// its store, and everything between is the same double arithmetic.
+template <typename T>
 __global__ __launch_bounds__(256) void tt_project_mfma(
-    const double *__restrict__ hij,   // [6][vol] complex128 interleaved
-    double *__restrict__ out,         // [6][vol] complex128 (may == hij)
+    const T *__restrict__ hij,        // [6][vol] complex, interleaved
+    T *__restrict__ out,              // [6][vol] complex (may == hij)
     const double *__restrict__ kx, const double *__restrict__ ky,
     const double *__restrict__ kz,
     int ny, int nz, long vol)
@@ -65,12 +70,12 @@ __global__ __launch_bounds__(256) void tt_project_mfma(
     const int bj = lane & 3;          // B col
     double h_re = 0.0, h_im = 0.0;    // A = H for M1 = H.P
     if (ai < 3 && ak < 3) {
-        typedef double d2 __attribute__((ext_vector_type(2)));
-        const d2 *p = (const d2 *)(hij
+        typedef T t2 __attribute__((ext_vector_type(2)));
+        const t2 *p = (const t2 *)(hij
             + ((long)sym_idx(ai, ak) * vol + site) * 2);
-        const d2 v = __builtin_nontemporal_load(p);
-        h_re = v.x;
-        h_im = v.y;
+        const t2 v = __builtin_nontemporal_load(p);
+        h_re = (double)v.x;
+        h_im = (double)v.y;
     }
     const double b_p = (ak < 3 && bj < 3) ? PEL(ak, bj) : 0.0;
     const double a_p = (ai < 3 && ak < 3) ? PEL(ai, ak) : 0.0;
@@ -102,20 +107,21 @@ __global__ __launch_bounds__(256) void tt_project_mfma(
         double re = m2_re - 0.5 * pab * tr_re;
         double im = m2_im - 0.5 * pab * tr_im;
         if (kzero) { re = 0.0; im = 0.0; }
-        typedef double d2 __attribute__((ext_vector_type(2)));
-        d2 v;
-        v.x = re;
-        v.y = im;
+        typedef T t2 __attribute__((ext_vector_type(2)));
+        t2 v;
+        v.x = (T)re;
+        v.y = (T)im;
         __builtin_nontemporal_store(
-            v, (d2 *)(out + ((long)sym_idx(ci, cj) * vol + site) * 2));
+            v, (t2 *)(out + ((long)sym_idx(ci, cj) * vol + site) * 2));
     }
 #undef PEL
 }
 
 }  // namespace
 
-extern "C" void launch_tt_project_mfma(
-    const double *hij, double *out, const double *kx, const double *ky,
+template <typename T>
+static void launch_tt(
+    const T *hij, T *out, const double *kx, const double *ky,
     const double *kz, int ny, int nz, long vol, hipStream_t stream)
 {
     const long waves = (vol + 3) / 4;
@@ -124,7 +130,21 @@ extern "C" void launch_tt_project_mfma(
     const long nblocks = (threads + block - 1) / block;
     const long gx = nblocks < 32768 ? nblocks : 32768;
     const long gy = (nblocks + gx - 1) / gx;
-    hipLaunchKernelGGL(tt_project_mfma, dim3((uint32_t)gx, (uint32_t)gy),
+    hipLaunchKernelGGL(tt_project_mfma<T>, dim3((uint32_t)gx, (uint32_t)gy),
                        dim3(block), 0, stream, hij, out, kx, ky, kz, ny,
                        nz, vol);
+}
+
+extern "C" void launch_tt_project_mfma(
+    const double *hij, double *out, const double *kx, const double *ky,
+    const double *kz, int ny, int nz, long vol, hipStream_t stream)
+{
+    launch_tt<double>(hij, out, kx, ky, kz, ny, nz, vol, stream);
+}
+
+extern "C" void launch_tt_project_mfma_c64(
+    const float *hij, float *out, const double *kx, const double *ky,
+    const double *kz, int ny, int nz, long vol, hipStream_t stream)
+{
+    launch_tt<float>(hij, out, kx, ky, kz, ny, nz, vol, stream);
 }

@@ -11,6 +11,8 @@ the k_x = k_y = 0 special case match the reference
 
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
@@ -88,21 +90,41 @@ class Projector:
 
     # ------------------------------------------------------------------
     def _gpu_fast(self, *tensors):
-        """All tensors CUDA complex128 contiguous with this projector's
-        k-space trailing shape → route to the fused one-launch kernels
-        (pystella_amd/backend/hip.py projector_op)."""
+        """The storage type of the fused one-launch kernels these
+        tensors route to (pystella_amd/backend/hip.py projector_op and
+        projector_op_c64), or None for the torch expressions.
+
+        All tensors CUDA, contiguous, of one complex type and with this
+        projector's k-space trailing shape: complex128 always takes the
+        fused kernels; complex64 only on a projector whose own transform
+        is float32, and not with PYSTELLA_OBS_C64=0."""
+        dtype = None
         for t in tensors:
             if not (isinstance(t, torch.Tensor) and t.is_cuda
-                    and t.dtype == torch.complex128 and t.is_contiguous()
+                    and t.is_contiguous()
                     and tuple(t.shape[-3:]) == self._kshape):
-                return False
-        return True
+                return None
+            if dtype is None:
+                dtype = t.dtype
+            elif t.dtype != dtype:
+                return None
+        if dtype == torch.complex128:
+            return dtype
+        if (dtype == torch.complex64
+                and self.fft.fk.dtype == torch.complex64
+                and os.environ.get("PYSTELLA_OBS_C64") != "0"):
+            return dtype
+        return None
 
-    def _run_op(self, op, tensors, times_abs_k=False):
-        from pystella_amd.backend.hip import projector_op
-        projector_op(op, self._kshape,
-                     [t.data_ptr() for t in tensors], self._eff_c,
-                     times_abs_k=times_abs_k)
+    def _run_op(self, op, tensors, ctype, times_abs_k=False):
+        from pystella_amd.backend import hip
+        if ctype == torch.complex64:
+            hip.projector_op_c64(op, self._kshape, tensors, self._eff_c,
+                                 times_abs_k=times_abs_k)
+        else:
+            hip.projector_op(op, self._kshape,
+                             [t.data_ptr() for t in tensors], self._eff_c,
+                             times_abs_k=times_abs_k)
 
     # ------------------------------------------------------------------
     def _zero_where_kvec_zero(self, x):
@@ -114,8 +136,9 @@ class Projector:
             vector, vector_T = queue, vector
             queue = None
         out = vector if vector_T is None else vector_T
-        if self._gpu_fast(vector, out):
-            self._run_op("transversify", [vector, out])
+        ctype = self._gpu_fast(vector, out)
+        if ctype is not None:
+            self._run_op("transversify", [vector, out], ctype)
             return out
         div = sum(self.kvec[mu] * vector[mu] for mu in range(3))
         ksq_safe = torch.where(self.ksq > 0, self.ksq,
@@ -130,8 +153,9 @@ class Projector:
         if isinstance(queue, torch.Tensor):
             plus, minus, vector = queue, plus, minus
             queue = None
-        if self._gpu_fast(vector, plus, minus):
-            self._run_op("vec_to_pol", [vector, plus, minus])
+        ctype = self._gpu_fast(vector, plus, minus)
+        if ctype is not None:
+            self._run_op("vec_to_pol", [vector, plus, minus], ctype)
             return plus, minus
         p = sum(vector[mu] * self.eps[mu].conj() for mu in range(3))
         m = sum(vector[mu] * self.eps[mu] for mu in range(3))
@@ -142,8 +166,9 @@ class Projector:
     def pol_to_vec(self, queue=None, plus=None, minus=None, vector=None):
         if isinstance(queue, torch.Tensor):
             queue, plus, minus, vector = None, queue, plus, minus
-        if self._gpu_fast(plus, minus, vector):
-            self._run_op("pol_to_vec", [plus, minus, vector])
+        ctype = self._gpu_fast(plus, minus, vector)
+        if ctype is not None:
+            self._run_op("pol_to_vec", [plus, minus, vector], ctype)
             return vector
         res = [plus * self.eps[mu] + minus * self.eps[mu].conj()
                for mu in range(3)]
@@ -158,9 +183,10 @@ class Projector:
         if isinstance(queue, torch.Tensor):
             queue, vector, plus, minus, lng = \
                 None, queue, vector, plus, minus
-        if self._gpu_fast(vector, plus, minus, lng):
+        ctype = self._gpu_fast(vector, plus, minus, lng)
+        if ctype is not None:
             self._run_op("decompose_vector", [vector, plus, minus, lng],
-                         times_abs_k=times_abs_k)
+                         ctype, times_abs_k=times_abs_k)
             return plus, minus, lng
         # compute the divergence BEFORE vec_to_pol stores: plus/minus
         # are routinely views of `vector` itself (the reference passes
@@ -182,9 +208,10 @@ class Projector:
         if isinstance(queue, torch.Tensor):
             queue, plus, minus, lng, vector = \
                 None, queue, plus, minus, lng
-        if self._gpu_fast(plus, minus, lng, vector):
+        ctype = self._gpu_fast(plus, minus, lng, vector)
+        if ctype is not None:
             self._run_op("decomp_to_vec", [plus, minus, lng, vector],
-                         times_abs_k=times_abs_k)
+                         ctype, times_abs_k=times_abs_k)
             return vector
         kmag_safe = torch.where(self.kmag > 0, self.kmag,
                                 torch.ones_like(self.kmag))
@@ -211,11 +238,16 @@ class Projector:
             hij, hij_TT = queue, hij
             queue = None
         out = hij if hij_TT is None else hij_TT
-        if (self._gpu_fast(hij, out)
+        ctype = self._gpu_fast(hij, out)
+        if (ctype is not None
                 and tuple(hij.shape[:-3]) == (6,)
                 and tuple(out.shape[:-3]) == (6,)):
+            from pystella_amd.backend import hip
             from pystella_amd.backend.hip import _stream, ext
             kshape = self._kshape
+            if ctype == torch.complex64:
+                hip.tt_project_c64(hij, out, self._eff_c, kshape)
+                return out
             vol = int(np.prod(kshape))
             kx, ky, kz = self._eff_c
             ext().tt_project(hij.data_ptr(), out.data_ptr(),
@@ -250,8 +282,9 @@ class Projector:
     def tensor_to_pol(self, queue=None, plus=None, minus=None, hij=None):
         if isinstance(queue, torch.Tensor):
             queue, plus, minus, hij = None, queue, plus, minus
-        if self._gpu_fast(hij, plus, minus):
-            self._run_op("tensor_to_pol", [hij, plus, minus])
+        ctype = self._gpu_fast(hij, plus, minus)
+        if ctype is not None:
+            self._run_op("tensor_to_pol", [hij, plus, minus], ctype)
             return plus, minus
         p = 0
         m = 0
@@ -267,8 +300,9 @@ class Projector:
     def pol_to_tensor(self, queue=None, plus=None, minus=None, hij=None):
         if isinstance(queue, torch.Tensor):
             queue, plus, minus, hij = None, queue, plus, minus
-        if self._gpu_fast(plus, minus, hij):
-            self._run_op("pol_to_tensor", [plus, minus, hij])
+        ctype = self._gpu_fast(plus, minus, hij)
+        if ctype is not None:
+            self._run_op("pol_to_tensor", [plus, minus, hij], ctype)
             return hij
         res = []
         for a in range(1, 4):

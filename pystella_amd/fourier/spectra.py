@@ -9,6 +9,8 @@ GPU) followed by one packed all-reduce.
 
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
@@ -61,19 +63,28 @@ class PowerSpectra:
         (reference spectra.py:140-176).
 
         GPU path: LDS-binned HIP kernel (torch index_add_ serializes on
-        the ~500 global bins and is ~500× slower at 512³)."""
-        if (isinstance(fk, torch.Tensor) and fk.is_cuda
-                and fk.dtype == torch.complex128 and fk.is_contiguous()
-                and self.num_bins <= 4096):
-            from pystella_amd.backend.hip import spectra_bin
+        the ~500 global bins and is ~500× slower at 512³).  complex128
+        modes always take it; complex64 modes take its complex64 form
+        when this object's own transform is float32 and they have its
+        k-shape (PYSTELLA_OBS_C64=0 sends them to torch instead)."""
+        fused = (isinstance(fk, torch.Tensor) and fk.is_cuda
+                 and fk.is_contiguous() and self.num_bins <= 4096)
+        c64 = (fused and fk.dtype == torch.complex64
+               and self.fft.fk.dtype == torch.complex64
+               and tuple(fk.shape[-3:]) == tuple(self.kshape)
+               and fk.numel() == self._bin_idx.numel()
+               and os.environ.get("PYSTELLA_OBS_C64") != "0")
+        if fused and (fk.dtype == torch.complex128 or c64):
+            from pystella_amd.backend import hip
             wb = self._wbase_cache.get(k_power)
             if wb is None:
                 wb = (self._counts * self._kmags ** k_power
                       ).reshape(-1).to(torch.float64).contiguous()
                 self._wbase_cache[k_power] = wb
                 self._bidx32 = self._bin_idx.to(torch.int32).contiguous()
-            hist = spectra_bin(fk.reshape(-1), wb, self._bidx32,
-                               self.num_bins).cpu().numpy()
+            kernel = hip.spectra_bin_c64 if c64 else hip.spectra_bin
+            hist = kernel(fk.reshape(-1), wb, self._bidx32,
+                          self.num_bins).cpu().numpy()
         else:
             w = (self._counts * self._kmags ** k_power
                  * torch.abs(fk) ** 2).reshape(-1)
