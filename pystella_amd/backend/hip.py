@@ -1322,7 +1322,8 @@ def tt_project_c64(hij, out, eff, kshape):
 # one launch per operation, fk read once, no k-space temporaries
 # (reference pystella/fourier/derivs.py:93-108 and poisson.py:96-101
 # run each as ONE generated kernel; these close K13 and K14).  Complex
-# values move as one 16-byte access per mode.  Every product that is
+# values move as one 16-byte access per mode (8 bytes in the complex64
+# forms, whose arithmetic is the same doubles).  Every product that is
 # then added goes through rounded(): the JIT compiles with
 # -ffp-contract=fast, which fuses even under a contract(off) pragma, and
 # a fused multiply-add is not the torch chain's result.  The empty asm
@@ -1348,31 +1349,57 @@ extern "C" __global__ __launch_bounds__(256) void {name}(
 KSPACE_DERIV_OUTS = ("pdx", "pdy", "pdz", "lap")
 
 
-def _kspace_derivs_pieces(outs):
-    params = ["const double2* __restrict__ fk"]
-    params += [f"double2* __restrict__ {o}" for o in outs]
+class _KspaceModes:
+    """How a kernel declares, loads and stores its modes.  The complex64
+    form differs from the complex128 one in nothing else: a stored mode
+    is one 8-byte access, widened to double on the load; every
+    expression is the complex128 form's, in double; a result is rounded
+    once, in the ``make_float2`` of its 8-byte store."""
+
+    def __init__(self, ctype):
+        self.c64 = ctype == "complex64"
+        self.elem = "float2" if self.c64 else "double2"
+
+    def load(self, name, ptr):
+        """Lines defining the ``const double2 name`` read from ``ptr``."""
+        if not self.c64:
+            return [f"const double2 {name} = {ptr}[idx];"]
+        return [f"const float2 {name}_s = {ptr}[idx];",
+                f"const double2 {name} = make_double2((double){name}_s.x, "
+                f"(double){name}_s.y);"]
+
+    def store(self, ptr, re, im):
+        """The line storing ``(re, im)``, two double expressions."""
+        if not self.c64:
+            return f"{ptr}[idx] = make_double2({re}, {im});"
+        return f"{ptr}[idx] = make_float2((float)({re}), (float)({im}));"
+
+
+def _kspace_derivs_pieces(outs, modes):
+    params = [f"const {modes.elem}* __restrict__ fk"]
+    params += [f"{modes.elem}* __restrict__ {o}" for o in outs]
     tables = [f"k1{'xyz'[mu]}" for mu in range(3) if f"pd{'xyz'[mu]}" in outs]
     if "lap" in outs:
         tables += ["k2x", "k2y", "k2z"]
     params += [f"const double* __restrict__ {t}" for t in tables]
     params.append("const double inv_n")
-    body = ["const double2 v = fk[idx];",
-            "const double2 t = make_double2(v.x * inv_n, v.y * inv_n);"]
+    body = modes.load("v", "fk") + [
+        "const double2 t = make_double2(v.x * inv_n, v.y * inv_n);"]
     for mu, (ax, i) in enumerate(zip("xyz", ("ii", "jj", "kk"))):
         if f"pd{ax}" in outs:
             body += [f"const double q{ax} = k1{ax}[{i}];",
-                     f"pd{ax}[idx] = make_double2(-q{ax} * t.y, "
-                     f"q{ax} * t.x);"]
+                     modes.store(f"pd{ax}", f"-q{ax} * t.y", f"q{ax} * t.x")]
     if "lap" in outs:
         body += ["const double kx = k2x[ii], ky = k2y[jj], kz = k2z[kk];",
                  "const double mk2 = -((rounded(kx * kx) + rounded(ky * ky))",
                  "                     + rounded(kz * kz));",
-                 "lap[idx] = make_double2(mk2 * t.x, mk2 * t.y);"]
+                 modes.store("lap", "mk2 * t.x", "mk2 * t.y")]
     return params, body
 
 
-def _kspace_pieces(op, flags):
+def _kspace_pieces(op, flags, modes):
     """(parameter list, body lines) of kernel ``op``; consumes ``flags``."""
+    elem = modes.elem
     if op == "derivs":
         outs = flags.pop("outs", None)
         if not outs or set(outs) - set(KSPACE_DERIV_OUTS):
@@ -1380,38 +1407,42 @@ def _kspace_pieces(op, flags):
                 f"outs must be a non-empty subset of {KSPACE_DERIV_OUTS}, "
                 f"got {outs!r}")
         outs = tuple(o for o in KSPACE_DERIV_OUTS if o in outs)
-        params, body = _kspace_derivs_pieces(outs)
+        params, body = _kspace_derivs_pieces(outs, modes)
     elif op == "div_accum":
         mu = int(flags.pop("mu"))
         accumulate = bool(flags.pop("accumulate"))
         if mu not in (0, 1, 2):
             raise ValueError(f"mu must be 0, 1 or 2, got {mu}")
-        params = ["const double2* __restrict__ fk",
-                  "double2* __restrict__ div_k",
+        params = [f"const {elem}* __restrict__ fk",
+                  f"{elem}* __restrict__ div_k",
                   "const double* __restrict__ k1", "const double inv_n"]
-        body = ["const double2 v = fk[idx];",
-                f"const double q = k1[{('ii', 'jj', 'kk')[mu]}];",
-                "double2 term = make_double2((-q * v.y) * inv_n, "
-                "(q * v.x) * inv_n);"]
+        body = modes.load("v", "fk") + [
+            f"const double q = k1[{('ii', 'jj', 'kk')[mu]}];",
+            "double2 term = make_double2((-q * v.y) * inv_n, "
+            "(q * v.x) * inv_n);"]
         if accumulate:
-            body += ["const double2 d = div_k[idx];",
-                     "term = make_double2(d.x + rounded(term.x), "
-                     "d.y + rounded(term.y));"]
-        body.append("div_k[idx] = term;")
+            body += modes.load("d", "div_k") + [
+                "term = make_double2(d.x + rounded(term.x), "
+                "d.y + rounded(term.y));"]
+        body.append(modes.store("div_k", "term.x", "term.y") if modes.c64
+                    else "div_k[idx] = term;")
     elif op == "poisson":
         # sol may be rhok itself: no __restrict__ on either
-        params = ["const double2* rhok", "double2* sol",
+        params = [f"const {elem}* rhok", f"{elem}* sol",
                   "const double* __restrict__ ex",
                   "const double* __restrict__ ey",
                   "const double* __restrict__ ez",
                   "const double inv_n", "const double m_squared"]
-        body = ["const double mk2 = (ex[ii] + ey[jj]) + ez[kk];",
-                "const double2 v = rhok[idx];",
-                "const double den = mk2 - m_squared;",
-                "sol[idx] = (mk2 < 0.0)",
-                "    ? make_double2((v.x * inv_n) / den, "
-                "(v.y * inv_n) / den)",
-                "    : make_double2(0.0, 0.0);"]
+        body = ["const double mk2 = (ex[ii] + ey[jj]) + ez[kk];"]
+        body += modes.load("v", "rhok") + [
+            "const double den = mk2 - m_squared;",
+            "const double2 r = (mk2 < 0.0)" if modes.c64
+            else "sol[idx] = (mk2 < 0.0)",
+            "    ? make_double2((v.x * inv_n) / den, "
+            "(v.y * inv_n) / den)",
+            "    : make_double2(0.0, 0.0);"]
+        if modes.c64:
+            body.append(modes.store("sol", "r.x", "r.y"))
     else:
         raise ValueError(f"unknown k-space op {op!r}")
     if flags:
@@ -1419,28 +1450,37 @@ def _kspace_pieces(op, flags):
     return params, body
 
 
-def kspace_source(op, kshape, **flags):
+def _kspace_kernel_name(op, ctype):
+    return f"kspace_{op}" + ("_c64" if ctype == "complex64" else "")
+
+
+def kspace_source(op, kshape, ctype="complex128", **flags):
     """HIP source of k-space kernel ``op`` (``"derivs"`` with
     ``outs=``, ``"div_accum"`` with ``mu=`` and ``accumulate=``,
-    ``"poisson"``) over k-space ``kshape``.  Needs no device."""
-    params, body = _kspace_pieces(op, dict(flags))
+    ``"poisson"``) over k-space ``kshape``; ``ctype`` is the storage
+    type of the modes (tables and scalars are double either way).
+    Needs no device."""
+    ctype = _ctype_name(ctype)
+    params, body = _kspace_pieces(op, dict(flags), _KspaceModes(ctype))
     head = (f"#define NKX {kshape[0]}\n"
             f"#define NKY {kshape[1]}\n"
             f"#define NKZ {kshape[2]}\n"
             "#define VOLK ((long)NKX * NKY * NKZ)\n")
     return head + KSPACE_KERNEL.format(
-        name=f"kspace_{op}", params=",\n    ".join(params),
+        name=_kspace_kernel_name(op, ctype), params=",\n    ".join(params),
         body="\n    ".join(body))
 
 
 _kspace_cache = {}
 
 
-def _kspace_complex(name, t, kshape=None):
+def _kspace_complex(name, t, kshape=None, ctype="complex128"):
     _check_tensor(name, t)
-    if t.dtype != torch.complex128:
-        raise TypeError(f"argument {name} has dtype {t.dtype}; the k-space "
-                        "kernels take complex128")
+    if t.dtype != getattr(torch, ctype):
+        kernels = ("k-space" if ctype == "complex128"
+                   else f"{ctype} k-space")
+        raise TypeError(f"argument {name} has dtype {t.dtype}; the "
+                        f"{kernels} kernels take {ctype}")
     if t.dim() != 3 or (kshape is not None and tuple(t.shape) != kshape):
         raise ValueError(f"argument {name} has shape {tuple(t.shape)}, "
                          f"expected {kshape or 'a 3-D k-space array'}")
@@ -1457,14 +1497,14 @@ def _kspace_table(name, t, n):
                          f"expected ({n},)")
 
 
-def _kspace_launch(op, kshape, ptrs, doubles, **flags):
+def _kspace_launch(op, kshape, ctype, ptrs, doubles, **flags):
     """``flags`` as the entry points normalise them (``outs`` in
     KSPACE_DERIV_OUTS order, ``mu`` an int, ``accumulate`` a bool)."""
-    key = (op, kshape) + tuple(sorted(flags.items()))
+    key = (op, kshape, ctype) + tuple(sorted(flags.items()))
     kid = _kspace_cache.get(key)
     if kid is None:
-        kid = ext().jit_compile(kspace_source(op, kshape, **flags),
-                                f"kspace_{op}")
+        kid = ext().jit_compile(kspace_source(op, kshape, ctype, **flags),
+                                _kspace_kernel_name(op, ctype))
         _kspace_cache[key] = kid
     vol = int(np.prod(kshape))
     if vol == 0:
@@ -1473,23 +1513,15 @@ def _kspace_launch(op, kshape, ptrs, doubles, **flags):
                      ptrs, [], doubles)
 
 
-def kspace_derivs(fk, outs, k1, k2, inv_n):
-    """One launch: read ``fk`` once, write the requested spectral
-    derivatives of ``t = fk * inv_n``.
-
-    :arg outs: dict mapping any non-empty subset of ``pdx``, ``pdy``,
-        ``pdz`` (``i k1_mu t``) and ``lap`` (``-|k2|^2 t``) to contiguous
-        complex128 device tensors of ``fk``'s shape; none may be ``fk``.
-    :arg k1, k2: the three per-axis float64 tables, flat on the device.
-    """
+def _kspace_derivs(ctype, fk, outs, k1, k2, inv_n):
     if not isinstance(outs, dict) or not outs \
             or set(outs) - set(KSPACE_DERIV_OUTS):
         raise ValueError("outs must map a non-empty subset of "
                          f"{KSPACE_DERIV_OUTS} to tensors")
-    kshape = _kspace_complex("fk", fk)
+    kshape = _kspace_complex("fk", fk, ctype=ctype)
     names = tuple(o for o in KSPACE_DERIV_OUTS if o in outs)
     for o in names:
-        _kspace_complex(o, outs[o], kshape)
+        _kspace_complex(o, outs[o], kshape, ctype)
         if outs[o].data_ptr() == fk.data_ptr():
             raise ValueError(f"output {o} aliases fk")
     if len({outs[o].data_ptr() for o in names}) != len(names):
@@ -1502,22 +1534,49 @@ def kspace_derivs(fk, outs, k1, k2, inv_n):
              if f"pd{'xyz'[mu]}" in names]
     if "lap" in names:
         ptrs += [k.data_ptr() for k in k2]
-    _kspace_launch("derivs", kshape, ptrs, [float(inv_n)], outs=names)
+    _kspace_launch("derivs", kshape, ctype, ptrs, [float(inv_n)], outs=names)
 
 
-def kspace_div_accum(fk, div_k, k1_mu, mu, inv_n, accumulate):
-    """One launch: ``term = (i k1_mu fk) * inv_n``, stored to ``div_k``
-    (``accumulate=False``) or added to it.  ``div_k`` may not be ``fk``."""
-    kshape = _kspace_complex("fk", fk)
-    _kspace_complex("div_k", div_k, kshape)
+def _kspace_div_accum(ctype, fk, div_k, k1_mu, mu, inv_n, accumulate):
+    kshape = _kspace_complex("fk", fk, ctype=ctype)
+    _kspace_complex("div_k", div_k, kshape, ctype)
     if mu not in (0, 1, 2):
         raise ValueError(f"mu must be 0, 1 or 2, got {mu}")
     _kspace_table("k1_mu", k1_mu, kshape[mu])
     if div_k.data_ptr() == fk.data_ptr():
         raise ValueError("output div_k aliases fk")
-    _kspace_launch("div_accum", kshape,
+    _kspace_launch("div_accum", kshape, ctype,
                    [fk.data_ptr(), div_k.data_ptr(), k1_mu.data_ptr()],
                    [float(inv_n)], mu=mu, accumulate=bool(accumulate))
+
+
+def _kspace_poisson(ctype, rhok, sol, ex, ey, ez, inv_n, m_squared):
+    kshape = _kspace_complex("rhok", rhok, ctype=ctype)
+    _kspace_complex("sol", sol, kshape, ctype)
+    for name, t, n in zip(("ex", "ey", "ez"), (ex, ey, ez), kshape):
+        _kspace_table(name, t, n)
+    _kspace_launch("poisson", kshape, ctype,
+                   [rhok.data_ptr(), sol.data_ptr(), ex.data_ptr(),
+                    ey.data_ptr(), ez.data_ptr()],
+                   [float(inv_n), float(m_squared)])
+
+
+def kspace_derivs(fk, outs, k1, k2, inv_n):
+    """One launch: read ``fk`` once, write the requested spectral
+    derivatives of ``t = fk * inv_n``.
+
+    :arg outs: dict mapping any non-empty subset of ``pdx``, ``pdy``,
+        ``pdz`` (``i k1_mu t``) and ``lap`` (``-|k2|^2 t``) to contiguous
+        complex128 device tensors of ``fk``'s shape; none may be ``fk``.
+    :arg k1, k2: the three per-axis float64 tables, flat on the device.
+    """
+    _kspace_derivs("complex128", fk, outs, k1, k2, inv_n)
+
+
+def kspace_div_accum(fk, div_k, k1_mu, mu, inv_n, accumulate):
+    """One launch: ``term = (i k1_mu fk) * inv_n``, stored to ``div_k``
+    (``accumulate=False``) or added to it.  ``div_k`` may not be ``fk``."""
+    _kspace_div_accum("complex128", fk, div_k, k1_mu, mu, inv_n, accumulate)
 
 
 def kspace_poisson(rhok, sol, ex, ey, ez, inv_n, m_squared):
@@ -1526,14 +1585,30 @@ def kspace_poisson(rhok, sol, ex, ey, ez, inv_n, m_squared):
     is dropped for every mass).  The operation is purely per mode, so
     ``sol`` may be the same tensor as ``rhok``.  ``m_squared`` is a
     run-time argument: a new mass compiles nothing."""
-    kshape = _kspace_complex("rhok", rhok)
-    _kspace_complex("sol", sol, kshape)
-    for name, t, n in zip(("ex", "ey", "ez"), (ex, ey, ez), kshape):
-        _kspace_table(name, t, n)
-    _kspace_launch("poisson", kshape,
-                   [rhok.data_ptr(), sol.data_ptr(), ex.data_ptr(),
-                    ey.data_ptr(), ez.data_ptr()],
-                   [float(inv_n), float(m_squared)])
+    _kspace_poisson("complex128", rhok, sol, ex, ey, ez, inv_n, m_squared)
+
+
+# The complex64 twins: the same arguments and checks with complex64
+# modes and float64 tables.  Each stored mode is widened once to double,
+# the formulas above are evaluated in double in the same order, and each
+# real component of a result is rounded once to float32 on its store.
+
+def kspace_derivs_c64(fk, outs, k1, k2, inv_n):
+    """:func:`kspace_derivs` on complex64 modes: every stored output is
+    one float32 rounding of the double result."""
+    _kspace_derivs("complex64", fk, outs, k1, k2, inv_n)
+
+
+def kspace_div_accum_c64(fk, div_k, k1_mu, mu, inv_n, accumulate):
+    """:func:`kspace_div_accum` on complex64 modes: the stored ``div_k``
+    is one float32 rounding of the double term, or of the stored
+    ``div_k``, widened, plus the double term."""
+    _kspace_div_accum("complex64", fk, div_k, k1_mu, mu, inv_n, accumulate)
+
+
+def kspace_poisson_c64(rhok, sol, ex, ey, ez, inv_n, m_squared):
+    """:func:`kspace_poisson` on complex64 modes, in place or not."""
+    _kspace_poisson("complex64", rhok, sol, ex, ey, ez, inv_n, m_squared)
 
 
 # ---------------------------------------------------------------------------
