@@ -111,6 +111,22 @@ def main(args=None):
     proj.transverse_traceless(hij_k)
     tr = (hij_k[0] + hij_k[3] + hij_k[5]).abs().max()
     print("5b. TT projection trace residual:", float(tr))
+    # a user-written k-space map: a Gaussian filter, in place between
+    # the transforms
+    from pystella_amd.field import exp
+    fk_ = Field("fk")
+    kx, ky, kz = (Field(n, indices=(ix,))
+                  for n, ix in (("kx", "i"), ("ky", "j"), ("kz", "k")))
+    smooth = ps.KSpaceMap(
+        {fk_: fk_ * exp(-(kx**2 + ky**2 + kz**2) * ps.var("s"))})
+    before = float(fld.var())
+    modes = fft.dft(fld)
+    smooth(fk=modes, s=0.5 * (2 * dx[0] * dk[0])**2,
+           kx=fft.sub_k["momenta_x"], ky=fft.sub_k["momenta_y"],
+           kz=fft.sub_k["momenta_z"])
+    fft.idft(modes, fld)
+    print("5c. Gaussian-filtered field variance:", before, "->",
+          float(fld.var()))
 
     # -- 6. multigrid ---------------------------------------------------
     from pystella_amd.derivs import _LAP_COEFS, centered_diff

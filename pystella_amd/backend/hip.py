@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from pystella_amd.backend.codegen import (
-    Codegen, PREAMBLE, geometry_defines,
+    Codegen, KspaceCodegen, KSPACE_DTYPES, KSPACE_PREAMBLE, PREAMBLE,
+    geometry_defines,
 )
 
 _EXT = None
@@ -1609,6 +1610,129 @@ def kspace_div_accum_c64(fk, div_k, k1_mu, mu, inv_n, accumulate):
 def kspace_poisson_c64(rhok, sol, ex, ey, ez, inv_n, m_squared):
     """:func:`kspace_poisson` on complex64 modes, in place or not."""
     _kspace_poisson("complex64", rhok, sol, ex, ey, ez, inv_n, m_squared)
+
+
+# ---------------------------------------------------------------------------
+# user-written k-space maps (``KSpaceMap``, closes K1's complex half):
+# the launch shape of KSPACE_KERNEL (256 threads, one mode each, the
+# k-shape baked in) around statements that backend/codegen.py's
+# KspaceCodegen lowers.  Every pointer is typed by its tensor's dtype, so
+# a complex128 mode is one 16-byte access and a complex64 mode one of 8;
+# every loaded value is widened once to double, all arithmetic is double,
+# and each real component is rounded once, on its store.  The index
+# decode is emitted only for a map that reads a per-axis table, in 32-bit
+# arithmetic while the volume allows it.  Nothing shields products from
+# contraction here: a map's result is defined to a tolerance, not to the
+# bits of a torch chain.
+
+KSPACE_MAP_TEMPLATE = """#define NKX {nkx}
+#define NKY {nky}
+#define NKZ {nkz}
+#define VOLK ((long)NKX * NKY * NKZ)
+using real = double;
+{preamble}
+extern "C" __global__ __launch_bounds__(256) void {name}(
+    {params})
+{{
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= VOLK) return;
+    {decode}{body}
+}}
+"""
+
+_KSPACE_MAP_DECODE = {
+    # fewer than 2^31 modes: the decode needs no 64-bit division
+    True: ("const unsigned lin = (unsigned)idx;\n"
+           "    const int kk = (int)(lin % NKZ);\n"
+           "    const int jj = (int)((lin / NKZ) % NKY);\n"
+           "    const int ii = (int)(lin / (NKZ * NKY));\n"
+           "    (void)ii; (void)jj; (void)kk;\n    "),
+    False: ("const int kk = (int)(idx % NKZ);\n"
+            "    const int jj = (int)((idx / NKZ) % NKY);\n"
+            "    const int ii = (int)(idx / ((long)NKZ * NKY));\n"
+            "    (void)ii; (void)jj; (void)kk;\n    "),
+}
+
+
+def _kspace_map_dtype(name, dtype):
+    """The key of KSPACE_DTYPES for a torch dtype or its name."""
+    key = str(dtype).replace("torch.", "")
+    if key not in KSPACE_DTYPES:
+        raise TypeError(
+            f"argument {name} has dtype {dtype}; a k-space map takes "
+            f"{sorted(KSPACE_DTYPES)}")
+    return key
+
+
+class JitKspaceMap:
+    """A compiled complex k-space map over k-space ``kshape``.
+
+    :arg field_args: the :class:`FieldArg`\\ s of the grid fields and the
+        per-axis tables (``axis`` 0, 1 or 2); their order is the
+        pointers'.
+    :arg dtypes: ``{name: dtype}`` of every one of them, torch dtypes or
+        their names.
+
+    ``compile=False`` only generates ``self.source``.
+    """
+
+    def __init__(self, map_dict, tmp_instructions, field_args, dtypes,
+                 kshape, name="kspace_map", compile=True):
+        self.kshape = tuple(int(n) for n in kshape)
+        self.field_args = [fa for fa in field_args if fa.spatial]
+        self.dtypes = {fa.name: _kspace_map_dtype(fa.name, dtypes[fa.name])
+                       for fa in self.field_args}
+        for fa in self.field_args:
+            if fa.axis is not None and KSPACE_DTYPES[self.dtypes[fa.name]][1]:
+                raise TypeError(f"axis table {fa.name} has dtype "
+                                f"{self.dtypes[fa.name]}; tables are real")
+        cg = KspaceCodegen(field_args, self.dtypes)
+        body = cg.emit_statements(map_dict, tmp_instructions)
+        params = []
+        for fa in self.field_args:
+            elem = KSPACE_DTYPES[self.dtypes[fa.name]][0]
+            # a stored array may be read too, under the one name
+            params.append(f"{elem}* {fa.name}" if fa.name in cg.stored
+                          else f"const {elem}* __restrict__ {fa.name}")
+        params += [f"const double {c}" for c, _ in cg.scalars]
+        vol = int(np.prod(self.kshape))
+        self.source = KSPACE_MAP_TEMPLATE.format(
+            nkx=self.kshape[0], nky=self.kshape[1], nkz=self.kshape[2],
+            preamble=PREAMBLE + KSPACE_PREAMBLE, name=name,
+            params=",\n    ".join(params),
+            decode=_KSPACE_MAP_DECODE[vol < 2**31] if cg.uses_axes else "",
+            body="\n    ".join(body))
+        self.stored = frozenset(cg.stored)
+        self.scalar_keys = [k for _, k in cg.scalars]
+        self.blocks = (vol + 255) // 256
+        self.key = ext().jit_compile(self.source, name) if compile else None
+
+    def __call__(self, env):
+        """Launch on ``env``'s tensors, which the caller has checked
+        against ``kshape`` and ``dtypes``."""
+        if self.key is None:
+            raise RuntimeError(
+                "JitKspaceMap was built with compile=False (source only)")
+        ptrs = []
+        for fa in self.field_args:
+            t = _check_tensor(fa.name, env[fa.name])
+            if str(t.dtype) != "torch." + self.dtypes[fa.name]:
+                raise TypeError(
+                    f"argument {fa.name} has dtype {t.dtype}, kernel "
+                    f"compiled for {self.dtypes[fa.name]}")
+            want = int(np.prod(fa.outer_shape, dtype=np.int64)) \
+                * int(np.prod(self.kshape)) if fa.axis is None \
+                else self.kshape[fa.axis]
+            if t.numel() != want:
+                raise ValueError(
+                    f"argument {fa.name} has {t.numel()} elements, the "
+                    f"kernel addresses {want}")
+            ptrs.append(t.data_ptr())
+        if self.blocks == 0:
+            return
+        doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
+        ext().jit_launch(self.key, self.blocks, 1, 1, 256, 1, 1, 0,
+                         _stream(), ptrs, [], doubles)
 
 
 # ---------------------------------------------------------------------------

@@ -26,6 +26,21 @@ _CALLS = {
 }
 
 
+def _imag(t):
+    return t.imag if t.is_complex() else torch.zeros_like(t)
+
+
+# calls that take a real or a complex argument (KSpaceMap); torch.exp of
+# a complex tensor is exp(re) (cos im, sin im)
+_CALLS.update({
+    "conj": torch.conj, "real": torch.real, "imag": _imag, "abs": torch.abs,
+})
+_NUMBER_CALLS = {
+    "conj": lambda x: x.conjugate(), "real": lambda x: x.real,
+    "imag": lambda x: x.imag, "abs": abs,
+}
+
+
 class EvalContext:
     """Grid geometry needed to slice interior views of padded arrays."""
 
@@ -64,6 +79,13 @@ def eval_field(f, outer_idx, env, ctx):
                 raise IndexError(f"scalar {f.name} indexed with {outer_idx}")
             return t[outer_idx]
         return t
+    if len(f.indices) == 1:
+        # a 1-D table along grid axis "i", "j" or "k", broadcast over
+        # the other two
+        axis = ("i", "j", "k").index(f.indices[0])
+        shape = [1, 1, 1]
+        shape[axis] = -1
+        return t.reshape(shape)
     if outer_idx:
         t = t[outer_idx]
     if f.is_padded:
@@ -121,6 +143,11 @@ def eval_expr(expr, env, ctx):
         args = [eval_expr(a, env, ctx) for a in expr.args]
         if all(isinstance(a, numbers.Number) for a in args):
             import math
+            if expr.func in _NUMBER_CALLS:
+                return _NUMBER_CALLS[expr.func](args[0])
+            if expr.func == "exp" and isinstance(args[0], complex):
+                import cmath
+                return cmath.exp(args[0])
             if expr.func == "fabs":
                 return abs(args[0])
             if expr.func in ("fmin", "min"):
@@ -174,6 +201,8 @@ def _store(lhs, value, env, ctx):
     if isinstance(view, torch.Tensor):
         if isinstance(value, torch.Tensor):
             view.copy_(value)
+        elif isinstance(value, complex):
+            view.fill_(value)
         else:
             view.fill_(float(value))
     else:

@@ -24,6 +24,7 @@ from pystella_amd.field.expr import (  # noqa: F401
     Expr, Variable, Subscript, Sum, Product, Quotient, Power, Call,
     Comparison, If, var, is_number, is_zero,
     sin, cos, tan, exp, log, sqrt, tanh, sinh, cosh, fabs, fmin, fmax,
+    conj, real, imag, abs,
 )
 
 __all__ = [
@@ -299,6 +300,17 @@ class FieldArg:
     padded: bool
     spatial: bool
     dtype: object = None
+    # 0, 1 or 2 for a 1-D table along that grid axis (a Field whose only
+    # index is "i", "j" or "k"); None for every other field
+    axis: object = None
+
+
+def field_axis(f):
+    """The grid axis of a 1-D table field (``indices=("j",)`` is 1), or
+    None for a field that is not one."""
+    if len(f.indices) == 1 and f.indices[0] in ("i", "j", "k"):
+        return ("i", "j", "k").index(f.indices[0])
+    return None
 
 
 def get_field_args(expressions, prepend_with=None):
@@ -310,7 +322,7 @@ def get_field_args(expressions, prepend_with=None):
         outer = tuple(prepend_with or ()) + f.shape
         arg = FieldArg(name=f.name, outer_shape=outer,
                        padded=f.is_padded, spatial=f.is_spatial,
-                       dtype=f.dtype)
+                       dtype=f.dtype, axis=field_axis(f))
         prev = args.get(f.name)
         if prev is not None and prev != arg:
             raise ValueError(

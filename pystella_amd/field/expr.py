@@ -17,6 +17,8 @@ structurally hashable so they can key ``rhs_dict``-style dictionaries.
 
 from __future__ import annotations
 
+import builtins
+import cmath
 import math
 import numbers
 
@@ -96,6 +98,9 @@ class Expr:
 
     def __pos__(self):
         return self
+
+    def __abs__(self):
+        return Call("abs", (self,))
 
     def __mul__(self, other):
         other = _wrapped(other)
@@ -311,13 +316,22 @@ def _make_fn(name, pyfn):
 sin = _make_fn("sin", math.sin)
 cos = _make_fn("cos", math.cos)
 tan = _make_fn("tan", math.tan)
-exp = _make_fn("exp", math.exp)
+exp = _make_fn("exp", lambda x: cmath.exp(x) if isinstance(x, complex)
+               else math.exp(x))
 log = _make_fn("log", math.log)
 sqrt = _make_fn("sqrt", math.sqrt)
 tanh = _make_fn("tanh", math.tanh)
 sinh = _make_fn("sinh", math.sinh)
 cosh = _make_fn("cosh", math.cosh)
-fabs = _make_fn("fabs", abs)
+fabs = _make_fn("fabs", builtins.abs)
+
+# complex-aware calls (KSpaceMap): each accepts a real or a complex
+# argument; ``abs`` is the modulus, also reached by the builtin through
+# ``Expr.__abs__``
+conj = _make_fn("conj", lambda x: x.conjugate())
+real = _make_fn("real", lambda x: x.real)
+imag = _make_fn("imag", lambda x: x.imag)
+abs = _make_fn("abs", builtins.abs)     # noqa: A001
 
 
 def fmin(a, b):
