@@ -142,6 +142,26 @@ def test_bench_distributed_gws_cpu(tmp_path):
     assert d["config"]["model"] == "scalar_preheating+gw"
 
 
+def test_bench_gws_split_cpu():
+    """bench.py --gws --gws-split end to end on the CPU (one process):
+    the two three-component tensor families that are views of one
+    parent array."""
+    import json
+    import subprocess
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(repo, "bench.py"),
+           "--gpus", "1", "--steps", "1", "--warmup", "0",
+           "--grid", "16", "--device", "cpu", "--gws", "--gws-split"]
+    out = subprocess.run(cmd, cwd=repo, capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 0, out.stderr[-1500:]
+    line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
+    d = json.loads(line)
+    assert d["config"]["model"] == "scalar_preheating+gw"
+    assert d["steps"] == 1
+    assert np.isfinite(d["value"]) and d["value"] > 0
+
+
 def test_bench_8rank_cpu(tmp_path):
     """8-rank (2,2,2) bench on gloo — the exact topology of the
     driver's N=8 strong-scaling run."""

@@ -26,7 +26,7 @@ import pystella_amd as ps
 from pystella_amd.backend.hip import JitLapStage
 from pystella_amd.sectors import get_rho_and_p
 from tests.preheat_reference import (
-    MPL, initial_data, potential, preheat_reference)
+    MPL, gw_reference, initial_data, potential, preheat_reference)
 
 pytestmark = pytest.mark.gpu
 
@@ -45,11 +45,27 @@ KNOBS = ("PYSTELLA_TILE", "PYSTELLA_PERIODIC", "PYSTELLA_SHELL",
          "PYSTELLA_SECTIONS", "PYSTELLA_KEEP_LASTK")
 
 
+def tableau(stepper):
+    """The ``(A, B)`` arguments of the reference for the framework's
+    ``stepper`` class: RK54 keeps the reference's own literal table."""
+    if stepper == "LowStorageRK54":
+        return {}
+    cls = getattr(ps, stepper)
+    return {"A": tuple(float(x) for x in cls._A),
+            "B": tuple(float(x) for x in cls._B)}
+
+
 @functools.lru_cache(maxsize=None)
-def reference(h):
-    """One numpy integration per halo order, shared by every case."""
+def reference(h, stepper="LowStorageRK54"):
+    """One numpy integration per halo order (and tableau), shared by
+    every case."""
     f0, df0 = initial_data(GRID)
-    out = preheat_reference(f0, df0, DX, DT, STEPS, h)
+    if stepper == "LowStorageRK54":
+        out = preheat_reference(f0, df0, DX, DT, STEPS, h)
+    else:
+        fr, dfr, _, _, ar, adr, energies = gw_reference(
+            f0, df0, None, None, DX, DT, STEPS, h, **tableau(stepper))
+        out = fr, dfr, ar, adr, energies
     for arr in out[:2]:
         arr.setflags(write=False)
     return out
@@ -67,10 +83,11 @@ def _check_energy(what, E, P, Er, Pr):
     assert eP < 1e-10, (what, P, Pr)
 
 
-def run_and_check(monkeypatch, h, tile, periodic, split=False, knobs=None):
-    """Two device-resident RK54 steps with the stage kernel forced to
-    ``tile`` / ``periodic``; every compared quantity is printed, then
-    asserted against the numpy reference."""
+def run_and_check(monkeypatch, h, tile, periodic, split=False, knobs=None,
+                  stepper="LowStorageRK54"):
+    """Two device-resident steps of the 2N-storage ``stepper`` with the
+    stage kernel forced to ``tile`` / ``periodic``; every compared
+    quantity is printed, then asserted against the numpy reference."""
     from pystella_amd.fusion import (
         DeviceFriedmannLoop, FusedLaplacianReduction, StencilRKStepper)
     for name in KNOBS:
@@ -80,7 +97,9 @@ def run_and_check(monkeypatch, h, tile, periodic, split=False, knobs=None):
     for name, value in (knobs or {}).items():
         monkeypatch.setenv(name, value)
 
-    fr, dfr, ar, adr, energies = reference(h)
+    Stepper = getattr(ps, stepper)
+    ns = Stepper.num_stages
+    fr, dfr, ar, adr, energies = reference(h, stepper)
     f0, df0 = initial_data(GRID)
     gsize = float(np.prod(GRID))
     decomp = ps.DomainDecomposition((1, 1, 1), h, rank_shape=GRID)
@@ -93,7 +112,7 @@ def run_and_check(monkeypatch, h, tile, periodic, split=False, knobs=None):
     f[cut] = torch.as_tensor(f0)
     dfdt[cut] = torch.as_tensor(df0)
 
-    st = StencilRKStepper(ps.LowStorageRK54, [sector], derivs,
+    st = StencilRKStepper(Stepper, [sector], derivs,
                           halo_shape=h, rank_shape=GRID, dt=DT,
                           reducers=sector, grid_size=gsize,
                           callback=get_rho_and_p)
@@ -108,7 +127,7 @@ def run_and_check(monkeypatch, h, tile, periodic, split=False, knobs=None):
     _check_energy("seed reduction", _scalar(e0["total"]),
                   _scalar(e0["pressure"]), *energies[0])
 
-    ex = ps.Expansion(e0["total"], ps.LowStorageRK54, mpl=MPL)
+    ex = ps.Expansion(e0["total"], Stepper, mpl=MPL)
     decomp.share_halos(arrays["f"])
     dl = DeviceFriedmannLoop(st, decomp, ex, gsize, DT, mpl=MPL)
     if split:
@@ -148,7 +167,8 @@ def run_and_check(monkeypatch, h, tile, periodic, split=False, knobs=None):
     # per-step (E, P): the pair fed to the last stage's Friedmann update
     for n, state in enumerate(states):
         _check_energy(f"step {n} last stage", float(state["energy"]),
-                      float(state["pressure"]), *energies[5 * n + 4])
+                      float(state["pressure"]),
+                      *energies[ns * n + ns - 1])
 
     fg = arrays["f"].cpu()[cut].numpy()
     dfg = arrays["dfdt"].cpu()[cut].numpy()
@@ -207,3 +227,13 @@ def test_stage_region_split_forms(tile, form, monkeypatch):
     assert len(slabs) == 6
     # the split really happened: one launch group per region
     assert len(dl._nblks) == (2 if form == "shell" else 7), dl._nblks
+
+
+@requires_gpu
+@pytest.mark.parametrize("periodic", ["0", "1"])
+def test_stage_rk144(periodic, monkeypatch):
+    """A fourteen-stage 2N tableau through the stage kernels and the
+    device loop at the smallest tile: the last-stage k-store elision
+    keys on ``num_stages`` and ``_A[0] == 0``, not on RK54."""
+    run_and_check(monkeypatch, 2, TILES[-1], periodic,
+                  stepper="LowStorageRK144")
