@@ -1971,6 +1971,305 @@ def rayleigh_modes(fk, dfk, sqrt_power, omega, tables, grid_shape, seed,
 
 
 # ---------------------------------------------------------------------------
+# multigrid transfers (K15/K16): restriction and prolongation between a
+# halo-padded fine array f1 (interior 2*n2 per axis) and a halo-padded
+# coarse array f2 (interior n2), one launch each.  The per-axis
+# coefficients and the halo are baked in as literals; the coarse extents
+# and the number of outer slices are run-time ints, so one operator
+# compiles once per dtype and serves every level.  Every loaded value is
+# widened once to double, the tensor-product sum is evaluated in double
+# one axis after the other (in the torch chain's order: x, y, z for
+# restriction, z, y, x for prolongation), and each stored value is
+# rounded once to ``real``; the ``correct`` forms store one rounding of
+# ``(double)old - R(f1)`` and ``(double)old + I(f2)``.  Products may
+# contract into multiply-adds: the result is defined to rounding, not to
+# the bits of the torch chain in multigrid/transfer.py.
+#
+# A block is MG_TY waves; a wave is 64 consecutive sites of one z-row of
+# the kernel's lane axis (coarse k for restriction, fine k for
+# prolongation), the block's waves are MG_TY consecutive coarse j, and
+# each thread walks MG_XI consecutive coarse i.  Rows and planes that
+# neighbouring sites share are therefore re-read from L1/L2 by the same
+# block shortly after their first read.  Tiles never straddle an outer
+# slice; the grid is capped and strides over the tiles.  Only interior
+# sites of the output are stored.
+
+MG_TY = 4
+MG_XI = 4
+_MG_GRID_CAP = 4096
+
+MG_TRANSFER_TEMPLATE = """#define H {halo}
+#define TY {ty}
+#define XI {xi}
+using real = {real};
+
+extern "C" __global__ __launch_bounds__(64 * TY) void {name}(
+    {params},
+    const int n2x, const int n2y, const int n2z, const int nouter)
+{{
+    const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;
+    // strides of the fine (1) and coarse (2) padded arrays
+    const long sy1 = 2L * n2z + 2 * H, sx1 = sy1 * (2L * n2y + 2 * H);
+    const long so1 = sx1 * (2L * n2x + 2 * H);
+    const long sy2 = (long)n2z + 2 * H, sx2 = sy2 * ((long)n2y + 2 * H);
+    const long so2 = sx2 * ((long)n2x + 2 * H);
+    const int nlz = {lane_extent};
+    const int ntz = (nlz + 63) / 64, nty = (n2y + TY - 1) / TY;
+    const int ntx = (n2x + XI - 1) / XI;
+    const long ntiles = (long)nouter * ntx * nty * ntz;
+    for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {{
+        const int tz = (int)(t % ntz);
+        long q = t / ntz;
+        const int ty = (int)(q % nty);
+        q /= nty;
+        const int tx = (int)(q % ntx);
+        const long o = q / ntx;
+        const int lz = tz * 64 + lane, j = ty * TY + row;
+        if (lz >= nlz || j >= n2y) continue;
+        const int i1 = (tx * XI + XI < n2x) ? tx * XI + XI : n2x;
+        for (int i = tx * XI; i < i1; ++i) {{
+            {body}
+        }}
+    }}
+}}
+"""
+
+
+def _mg_literal(c):
+    c = float(c)
+    if not math.isfinite(c):
+        raise ValueError(f"transfer coefficient {c} is not finite")
+    return repr(c)
+
+
+def _mg_offset(a, stride):
+    """``+ a * stride`` as source text (nothing for ``a == 0``)."""
+    if a == 0:
+        return ""
+    return f" {'+' if a > 0 else '-'} {abs(a)} * {stride}"
+
+
+def _mg_sum(terms):
+    """Source of ``Σ c * value`` over ``terms``, pairs of (coefficient,
+    double-valued source text); ``0.0`` for none."""
+    if not terms:
+        return "0.0"
+    return " + ".join(f"{_mg_literal(c)} * {v}" for c, v in terms)
+
+
+def _mg_axis_offsets(coefs, halo, what):
+    out = {}
+    for a, c in coefs.items():
+        if int(a) != a:
+            raise ValueError(f"{what} offset {a!r} is not an integer")
+        out[int(a)] = c
+    if not out:
+        raise ValueError(f"{what} coefficients are empty")
+    if max(abs(a) for a in out) > halo:
+        raise ValueError(
+            f"{what} offsets {sorted(out)} do not fit halo {halo}")
+    return dict(sorted(out.items()))
+
+
+def mg_interpolation_offsets(even, odd):
+    """The per-parity ``{coarse offset: coefficient}`` of a prolongation
+    (fine site ``2i + p`` takes ``Σ_a c_a f2[i + (p + a) // 2]``): the
+    rule of ``InterpolationBase._axis_coefs``."""
+    return tuple({(p + a) // 2: c for a, c in coefs.items()}
+                 for p, coefs in enumerate((even, odd)))
+
+
+def _mg_restrict_body(coefs, correct):
+    items = list(coefs.items())
+    lines = ["const real* __restrict__ p = f1 + o * so1 "
+             "+ (H + 2L * i) * sx1 + (H + 2L * j) * sy1 + (H + 2L * lz);"]
+    for na, (a, _) in enumerate(items):
+        for nb, (b, _) in enumerate(items):
+            lines.append(
+                f"const real* __restrict__ r{na}_{nb} = p"
+                f"{_mg_offset(a, 'sx1')}{_mg_offset(b, 'sy1')};")
+    # x, then y, then z, each in ascending offset: the torch chain's
+    # order, so that float64 results with coefficients whose products
+    # are exact (full weighting's) are the chain's, bit for bit
+    for nc, (cc, _) in enumerate(items):
+        for nb in range(len(items)):
+            lines.append(f"const double x{nb}_{nc} = " + _mg_sum(
+                [(c, f"(double)r{na}_{nb}[{cc}]")
+                 for na, (_, c) in enumerate(items)]) + ";")
+        lines.append(f"const double y{nc} = " + _mg_sum(
+            [(c, f"x{nb}_{nc}") for nb, (_, c) in enumerate(items)]) + ";")
+    lines.append("const double s = " + _mg_sum(
+        [(c, f"y{nc}") for nc, (_, c) in enumerate(items)]) + ";")
+    lines.append("const long d = o * so2 + (H + (long)i) * sx2 "
+                 "+ (H + (long)j) * sy2 + (H + lz);")
+    lines.append("f2[d] = (real)((double)f2[d] - s);" if correct
+                 else "f2[d] = (real)s;")
+    return lines
+
+
+def _mg_interpolate_body(par, correct):
+    # the union of both parities' coarse offsets: what the pair of fine
+    # sites 2i, 2i+1 reads along one axis
+    union = sorted(set(par[0]) | set(par[1]))
+    lines = ["const int pk = lz & 1;",
+             "const real* __restrict__ pc = f2 + o * so2 "
+             "+ (H + (long)i) * sx2 + (H + (long)j) * sy2 "
+             "+ (H + (lz >> 1));"]
+    # z: the lane's parity selects each coefficient, 0.0 where its
+    # parity does not read the site, and every lane loads the whole
+    # union.  Selecting the sums instead lets the compiler sink the
+    # loads of one parity under an exec-masked branch per load.  (A
+    # non-finite coarse value therefore reaches both fine sites of its
+    # pair, where the chain confines it to the parity that reads it.)
+    for nc, cc in enumerate(union):
+        lines.append(
+            f"const double cz{nc} = pk ? {_mg_literal(par[1].get(cc, 0.0))}"
+            f" : {_mg_literal(par[0].get(cc, 0.0))};")
+    for na, a in enumerate(union):
+        for nb, b in enumerate(union):
+            lines.append(
+                f"const real* __restrict__ r{na}_{nb} = pc"
+                f"{_mg_offset(a, 'sx2')}{_mg_offset(b, 'sy2')};")
+            lines.append(f"const double z{na}_{nb} = " + " + ".join(
+                f"cz{nc} * (double)r{na}_{nb}[{cc}]"
+                for nc, cc in enumerate(union)) + ";")
+    # y then x: both parities of both axes are this thread's, unrolled
+    for na, a in enumerate(union):
+        for pj in (0, 1):
+            lines.append(f"const double y{na}_{pj} = " + _mg_sum(
+                [(par[pj][b], f"z{na}_{nb}")
+                 for nb, b in enumerate(union) if b in par[pj]]) + ";")
+    lines.append("const long d = o * so1 + (H + 2L * i) * sx1 "
+                 "+ (H + 2L * j) * sy1 + (H + lz);")
+    for pi in (0, 1):
+        for pj in (0, 1):
+            val = _mg_sum([(par[pi][a], f"y{na}_{pj}")
+                           for na, a in enumerate(union) if a in par[pi]])
+            at = "d" + (" + sx1" if pi else "") + (" + sy1" if pj else "")
+            lines.append(f"const double s{pi}{pj} = {val};")
+            lines.append(
+                f"f1[{at}] = (real)((double)f1[{at}] + s{pi}{pj});"
+                if correct else f"f1[{at}] = (real)s{pi}{pj};")
+    return lines
+
+
+def _mg_kernel_name(kind, correct):
+    return f"mg_{kind}" + ("_correct" if correct else "")
+
+
+def _mg_dtype(dtype):
+    if isinstance(dtype, str):
+        dtype = getattr(torch, dtype, None)
+    if dtype not in _RTYPE:
+        raise TypeError(
+            f"multigrid transfers take float32 or float64, got {dtype}")
+    return dtype
+
+
+def mg_transfer_source(kind, coefs, halo, dtype, correct=False):
+    """HIP source of a multigrid transfer kernel.  ``kind`` is
+    ``"restrict"`` with ``coefs`` the per-axis ``{fine offset:
+    coefficient}``, or ``"interpolate"`` with ``coefs`` the pair
+    ``(even, odd)`` of per-axis ``{offset: coefficient}`` of the even
+    and odd fine sites.  ``halo`` is the padding of both arrays and
+    ``dtype`` their element type.  Needs no device."""
+    halo = int(halo)
+    correct = bool(correct)
+    real = _RTYPE[_mg_dtype(dtype)]
+    if kind == "restrict":
+        body = _mg_restrict_body(
+            _mg_axis_offsets(coefs, halo, "restriction"), correct)
+        params = ["const real* __restrict__ f1", "real* __restrict__ f2"]
+        lane_extent = "n2z"
+    elif kind == "interpolate":
+        even, odd = coefs
+        par = tuple(_mg_axis_offsets(c, halo, "prolongation") for c in
+                    mg_interpolation_offsets(even, odd))
+        body = _mg_interpolate_body(par, correct)
+        params = ["real* __restrict__ f1", "const real* __restrict__ f2"]
+        lane_extent = "2 * n2z"
+    else:
+        raise ValueError(f"unknown transfer kind {kind!r}")
+    return MG_TRANSFER_TEMPLATE.format(
+        halo=halo, ty=MG_TY, xi=MG_XI, real=real,
+        name=_mg_kernel_name(kind, correct), params=",\n    ".join(params),
+        lane_extent=lane_extent, body="\n            ".join(body))
+
+
+_mg_cache = {}
+
+
+def mg_transfer_fits(f1, f2, halo):
+    """Whether fine ``f1`` and coarse ``f2`` are a pair the transfer
+    kernels take: contiguous device tensors on one device, both float32
+    or both float64, equal outer dimensions, last three dimensions
+    exactly ``2 n2 + 2 halo`` and ``n2 + 2 halo``, no shared memory."""
+    if not (isinstance(f1, torch.Tensor) and isinstance(f2, torch.Tensor)
+            and f1.is_cuda and f2.is_cuda and f1.device == f2.device
+            and f1.dtype == f2.dtype and f1.dtype in _RTYPE
+            and f1.dim() >= 3 and f1.dim() == f2.dim()
+            and f1.shape[:-3] == f2.shape[:-3]
+            and f1.is_contiguous() and f2.is_contiguous()):
+        return False
+    for s1, s2 in zip(f1.shape[-3:], f2.shape[-3:]):
+        n2 = s2 - 2 * halo
+        if n2 < 0 or s1 != 2 * n2 + 2 * halo:
+            return False
+    a, b = f1.data_ptr(), f2.data_ptr()
+    return (a + f1.numel() * f1.element_size() <= b
+            or b + f2.numel() * f2.element_size() <= a)
+
+
+def _mg_launch(kind, f1, f2, coefs, key, halo, correct):
+    halo = int(halo)
+    correct = bool(correct)
+    if not mg_transfer_fits(f1, f2, halo):
+        raise ValueError(
+            f"mg_{kind}: f1 {tuple(f1.shape)} {f1.dtype} and f2 "
+            f"{tuple(f2.shape)} {f2.dtype} are not a contiguous, "
+            f"non-overlapping fine/coarse pair at halo {halo}")
+    key = (kind, key, halo, f1.dtype, correct)
+    kid = _mg_cache.get(key)
+    if kid is None:
+        kid = ext().jit_compile(
+            mg_transfer_source(kind, coefs, halo, f1.dtype, correct),
+            _mg_kernel_name(kind, correct))
+        _mg_cache[key] = kid
+    n2 = [s - 2 * halo for s in f2.shape[-3:]]
+    nouter = 1
+    for s in f2.shape[:-3]:
+        nouter *= s
+    nlz = n2[2] if kind == "restrict" else 2 * n2[2]
+    ntiles = (nouter * ((n2[0] + MG_XI - 1) // MG_XI)
+              * ((n2[1] + MG_TY - 1) // MG_TY) * ((nlz + 63) // 64))
+    if ntiles == 0:
+        return
+    ext().jit_launch(kid, min(_MG_GRID_CAP, ntiles), 1, 1, 64 * MG_TY, 1, 1,
+                     0, _stream(), [f1.data_ptr(), f2.data_ptr()],
+                     n2 + [nouter], [])
+
+
+def _mg_key(coefs):
+    return tuple(sorted((int(a), float(c)) for a, c in coefs.items()))
+
+
+def mg_restrict(f1, f2, coefs, halo, correct):
+    """One launch, no allocation: the interior of coarse ``f2`` becomes
+    (``correct``: is reduced by) ``Σ_abc c_a c_b c_c f1[2i+a, 2j+b,
+    2k+c]`` of fine ``f1``.  Returns without a launch if the coarse
+    interior is empty."""
+    _mg_launch("restrict", f1, f2, coefs, _mg_key(coefs), halo, correct)
+
+
+def mg_interpolate(f1, f2, even, odd, halo, correct):
+    """One launch, no allocation: the interior of fine ``f1`` becomes
+    (``correct``: is increased by) the tensor-product prolongation of
+    coarse ``f2`` with per-axis coefficients ``even`` and ``odd``."""
+    _mg_launch("interpolate", f1, f2, (even, odd),
+               (_mg_key(even), _mg_key(odd)), halo, correct)
+
+
+# ---------------------------------------------------------------------------
 # AOT stencil kernels (csrc/derivs.hip)
 
 def _flat_fields(t, ndim_grid=3):

@@ -1,10 +1,17 @@
 """Inter-grid transfer operators (restriction / prolongation).
 
-Analogue of reference pystella/multigrid/transfer.py:40-264.  The
-tensor-product transfer stencils are implemented as strided tensor ops
-(every-other-point slices), which map to single strided-copy kernels on
-GPU; the hot multigrid cost is the smoother (see ``relax.py``), which
-runs through the fused HIP elementwise path.
+Analogue of reference pystella/multigrid/transfer.py:40-264.  On a GPU
+each call is one fused HIP kernel (backend/hip.py ``mg_restrict`` /
+``mg_interpolate``): every input is read once, the tensor-product sum is
+evaluated in double and each output is rounded once on its store, and
+nothing is allocated.  A call takes the kernel when ``f1`` and ``f2``
+are contiguous device tensors on one device that share no memory, both
+float32 or both float64, with equal outer dimensions and last three
+dimensions exactly ``2 n2 + 2h`` and ``n2 + 2h``, every stencil offset
+fits the halo, and ``PYSTELLA_MG_TRANSFER`` is not ``0``.  Every other
+call (CPU tensors, strided views, mixed dtypes, other shapes) runs the
+separable chain of strided tensor ops below, which rounds to the arrays'
+dtype after each per-axis pass.
 
 Conventions (match the reference): ``f1`` is the *fine*-grid array,
 ``f2`` the *coarse*-grid array; both are halo-padded.  ``correct=True``
@@ -13,10 +20,26 @@ variants apply the FAS corrections ``f2 -= R(f1)`` / ``f1 += I(f2)``.
 
 from __future__ import annotations
 
+import os
+
 
 __all__ = ["RestrictionBase", "FullWeighting", "Injection",
            "InterpolationBase", "LinearInterpolation",
            "CubicInterpolation"]
+
+
+def _fused(f1, f2, h, offsets):
+    """Whether this call runs as one fused HIP kernel (see the module
+    docstring); ``offsets`` are the stencil's offsets, on the grid whose
+    halo they reach into."""
+    if os.environ.get("PYSTELLA_MG_TRANSFER") == "0":
+        return False
+    if not (getattr(f1, "is_cuda", False) and getattr(f2, "is_cuda", False)):
+        return False
+    if any(int(a) != a or abs(a) > h for a in offsets):
+        return False
+    from pystella_amd.backend import hip
+    return hip.mg_transfer_fits(f1, f2, h)
 
 
 class RestrictionBase:
@@ -30,6 +53,10 @@ class RestrictionBase:
 
     def __call__(self, queue=None, f1=None, f2=None):
         h = self.h
+        if _fused(f1, f2, h, self.coefs):
+            from pystella_amd.backend import hip
+            hip.mg_restrict(f1, f2, self.coefs, h, self.correct)
+            return f2
         n2 = tuple(s - 2 * h for s in f2.shape[-3:])
         # Separable tensor product: one strided pass per axis instead
         # of len(coefs)^3 full-grid passes (the reference's loopy
@@ -125,6 +152,11 @@ class InterpolationBase:
 
     def __call__(self, queue=None, f1=None, f2=None):
         h = self.h
+        if _fused(f1, f2, h, [a for p in (0, 1)
+                              for a in self._axis_coefs(p)]):
+            from pystella_amd.backend import hip
+            hip.mg_interpolate(f1, f2, self.even, self.odd, h, self.correct)
+            return f1
         n2 = tuple(s - 2 * h for s in f2.shape[-3:])
         # Separable per-axis doubling (3 passes) instead of 8 parity
         # cases x len(coefs)^3 full-grid passes.  The contiguous axis
