@@ -5,6 +5,26 @@ This module is the only place that touches the native extension
 that runs — if the extension is missing or fails to load, GPU calls
 raise immediately (no silent torch fallback; see repo instructions on
 native-code loading).
+
+Layout, top to bottom:
+
+* the host plumbing, written once: ``_JitKernel`` (parameter list,
+  compile or source only, argument checks, launch) with
+  ``_PartialsKernel`` for the kernels that leave per-block partials, and
+  for the function-style families ``_cached_kernel``, ``_launch_1d``,
+  ``_check_arg`` and ``_kshape_defines``;
+* the JIT families, each a template, its source generator (a ``Jit*``
+  class or a ``*_source`` function, none of which needs a device) and
+  its launch: elementwise, stencil, stage-reduction, wrap, reduction,
+  histogram, spectra binning, projectors, k-space derivatives and
+  Poisson, k-space maps, Rayleigh modes, multigrid transfers, the
+  register-ring Laplacian kernels and the Friedmann update;
+* the wrappers of the AOT kernels in csrc/ (``derivs``, ``divergence``,
+  ``tt_project_c64``).
+
+``tools/kernel_manifest.py`` hashes every family's generated source and
+records every family's launch arguments; a change here that means to
+move no kernel leaves both outputs as they were.
 """
 
 from __future__ import annotations
@@ -111,6 +131,207 @@ def _resolve_scalar(env, key):
 
 
 # ---------------------------------------------------------------------------
+# host plumbing of the JIT kernels, written once
+
+_RTYPE = {torch.float64: "double", torch.float32: "float"}
+
+
+def _spatial(field_args):
+    return [fa for fa in field_args if fa.spatial]
+
+
+class _JitKernel:
+    """Host side of a generated kernel: its C parameter list, compiling
+    it (or only keeping its source), checking its arguments and
+    launching it.
+
+    csrc/module.cpp's ``jit_launch`` passes the pointers, then the ints,
+    then the doubles.  :meth:`_declare` writes the signature in that
+    order and records the pointers' names and the scalars' keys in the
+    order it wrote them; :meth:`_pointers` and :meth:`_launch` read only
+    what it recorded.  So the order is decided here and nowhere else,
+    and a signature cannot disagree with its launch.  What the
+    environment does not name (the ``partials`` or ``hist`` buffer a
+    kernel allocates itself, a block of ints) is ``extra`` text to
+    ``_declare`` and follows the gathered pointers, or goes as ``ints``,
+    in the ``_launch`` call of the class that declared it.
+    """
+
+    # dynamic LDS of every launch
+    shmem = 0
+    # ``want``/``short`` are the expected dtype with and without "torch."
+    _dtype_error = ("argument {name} has dtype {got}, kernel compiled for "
+                    "{want}")
+
+    def _declare(self, cg, names, ptr, extra=(), scalar="double", sep=", "):
+        """The parameter list: pointers ``names`` declared ``ptr``
+        (``ptr __restrict__ name``, or what ``ptr(name)`` returns), the
+        ``extra`` declarations, then the run-time scalars that ``cg`` has
+        collected (so call this after the last emission)."""
+        self.ptr_names = list(names)
+        self.scalar_keys = [k for _, k in cg.scalars]
+        if not callable(ptr):
+            ptr = (ptr + " __restrict__ {}").format
+        return sep.join([ptr(n) for n in names] + list(extra)
+                        + [f"{scalar} {c}" for c, _ in cg.scalars])
+
+    def _declare_fields(self, cg, field_args, ptr, extra=()):
+        """:meth:`_declare` for the spatial ``field_args``, in their
+        order."""
+        self.field_args = _spatial(field_args)
+        return self._declare(cg, [fa.name for fa in self.field_args], ptr,
+                             extra)
+
+    def _build(self, src, name, compile):
+        """``compile=False``: source only, inspectable without a device;
+        such a kernel cannot be launched."""
+        self.source = src
+        self.key = ext().jit_compile(src, name) if compile else None
+
+    def _tiled(self, tile, rank_shape):
+        """Launch shape of a (TBZ, TBY, XCHUNK) tiling of the grid."""
+        self.grid = _tile_grid(tile, rank_shape)
+        self.block = tile[0] * tile[1]
+
+    def _require_compiled(self):
+        if self.key is None:
+            raise RuntimeError(
+                f"{type(self).__name__} was built with compile=False "
+                "(source only) and cannot be launched")
+
+    def _arg_dtype(self, name):
+        """The dtype the kernel reads pointer ``name`` as."""
+        return self.dtype
+
+    def _pointers(self, env):
+        """(pointers, device) of the kernel's array arguments.  Every
+        dtype is looked at first, before the device: the kernel would
+        read a buffer of another dtype as its own type, garbage, and
+        past the end of a narrower one."""
+        self._require_compiled()
+        for n in self.ptr_names:
+            t, want = env[n], self._arg_dtype(n)
+            if isinstance(t, torch.Tensor) and t.dtype != want:
+                raise TypeError(self._dtype_error.format(
+                    name=n, got=t.dtype, want=want, short=str(want)[6:]))
+        ptrs, dev = [], None
+        for n in self.ptr_names:
+            t = _check_tensor(n, env[n])
+            dev = t.device
+            ptrs.append(t.data_ptr())
+        return ptrs, dev
+
+    def _launch(self, key, grid, env, ptrs, ints=()):
+        doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
+        ext().jit_launch(key, grid[0], grid[1], grid[2], self.block, 1, 1,
+                         self.shmem, _stream(), ptrs, list(ints), doubles)
+
+    def __call__(self, env):
+        ptrs, _ = self._pointers(env)
+        self._launch(self.key, self.grid, env, ptrs)
+
+
+class _PartialsKernel(_JitKernel):
+    """A kernel whose blocks each leave one column of a float64
+    ``[nred, nblk]`` partials buffer (PARTIALS_TAIL), finished with
+    torch ops and one packed copy to the host."""
+
+    PARTIALS = "double* __restrict__ partials"
+
+    def _tiled(self, tile, rank_shape):
+        super()._tiled(tile, rank_shape)
+        self.nblk = self.grid[0] * self.grid[1] * self.grid[2]
+        self._partials = None
+
+    def launch_only(self, env, ints=()):
+        """Full-grid launch without finishing the reduction; returns the
+        raw per-block partials tensor [nred, nblk] that the kernel owns
+        (stream-ordered, no host synchronization).  It is allocated anew
+        when the device or the block count changed."""
+        ptrs, dev = self._pointers(env)
+        p = self._partials
+        if p is None or p.device != dev or p.shape[1] != self.nblk:
+            p = self._partials = torch.empty(
+                (len(self.entries), self.nblk), dtype=torch.float64,
+                device=dev)
+        self._launch(self.key, self.grid, env, ptrs + [p.data_ptr()], ints)
+        return p
+
+    def _finish(self, dev):
+        """Combine per-block partials on-device, one packed D2H copy."""
+        vals = torch.empty(len(self.entries), dtype=torch.float64,
+                           device=dev)
+        for r, (_, op) in enumerate(self.entries):
+            row = self._partials[r]
+            if op in ("sum", "avg"):
+                vals[r] = row.sum()
+            elif op == "prod":
+                vals[r] = row.prod()
+            elif op == "max":
+                vals[r] = row.max()
+            else:
+                vals[r] = row.min()
+        return vals.cpu().tolist()
+
+    def __call__(self, env):
+        return self._finish(self.launch_only(env).device)
+
+
+# the generic reductions word their dtype refusal in their own way
+_REDUCTION_DTYPE_ERROR = ("reduction argument '{name}' has dtype {got}, "
+                          "kernel expects {want}")
+
+
+# what the function-style families share
+
+def _cached_kernel(cache, key, name, make_source):
+    """The compiled kernel ``name`` under ``cache[key]``, compiled from
+    ``make_source()`` on first use."""
+    kid = cache.get(key)
+    if kid is None:
+        kid = cache[key] = ext().jit_compile(make_source(), name)
+    return kid
+
+
+def _blocks_1d(n, cap=None):
+    blocks = (n + 255) // 256
+    return blocks if cap is None else min(cap, blocks)
+
+
+def _launch_1d(kid, n, ptrs, ints=(), doubles=(), cap=None):
+    """Blocks of 256 threads over ``n`` sites, at most ``cap`` blocks."""
+    ext().jit_launch(kid, _blocks_1d(n, cap), 1, 1, 256, 1, 1, 0, _stream(),
+                     ptrs, list(ints), list(doubles))
+
+
+def _kshape_defines(kshape):
+    return (f"#define NKX {kshape[0]}\n"
+            f"#define NKY {kshape[1]}\n"
+            f"#define NKZ {kshape[2]}\n"
+            "#define VOLK ((long)NKX * NKY * NKZ)\n")
+
+
+def _check_arg(name, t, dtype, why, shape=None, ndim=None, numel=None):
+    """A contiguous device tensor of ``dtype`` (one, or a tuple of the
+    allowed ones), else a TypeError ending in ``why``; optionally of
+    ``shape``, of ``ndim`` dimensions, or of ``numel = (count, wording)``
+    elements."""
+    _check_tensor(name, t)
+    if t.dtype not in (dtype if isinstance(dtype, tuple) else (dtype,)):
+        raise TypeError(f"argument {name} has dtype {t.dtype}{why}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"argument {name} has shape {tuple(t.shape)}, "
+                         f"expected {tuple(shape)}")
+    if ndim is not None and t.dim() != ndim:
+        raise ValueError(f"argument {name} has shape {tuple(t.shape)}, "
+                         f"expected a {ndim}-D k-space array")
+    if numel is not None and t.numel() != numel[0]:
+        raise ValueError(f"argument {name} has {t.numel()} elements, "
+                         f"{numel[1]} {numel[0]}")
+    return t
+
+
+# ---------------------------------------------------------------------------
 # JIT'd elementwise map (fused RK stage kernels etc.)
 
 ELEMENTWISE_TEMPLATE = """{defines}
@@ -130,7 +351,7 @@ extern "C" __global__ __launch_bounds__(TBZ * TBY) void {name}(
 """
 
 
-def _tile_defines(tile, rank_shape):
+def _tile_defines(tile):
     tbz, tby, xchunk = tile
     return (f"#define TBZ {tbz}\n#define TBY {tby}\n"
             f"#define XCHUNK {xchunk}\n")
@@ -143,51 +364,27 @@ def _tile_grid(tile, rank_shape):
             (nx + xchunk - 1) // xchunk)
 
 
-_RTYPE = {torch.float64: "double", torch.float32: "float"}
-
-
-class JitElementwise:
+class JitElementwise(_JitKernel):
     """Compiled fused per-site map over the interior grid.  Supports
     fp64 and fp32 arrays (``using real = double|float`` baked into the
     kernel; run-time scalars stay double and are cast on use)."""
 
     def __init__(self, map_dict, tmp_instructions, field_args, scalar_names,
                  halo, rank_shape, name="ew_map", tile=(64, 4, 64),
-                 dtype=torch.float64):
+                 dtype=torch.float64, compile=True):
         self.rank_shape = tuple(rank_shape)
         self.tile = tile
         self.dtype = dtype
-        self.field_args = [fa for fa in field_args if fa.spatial]
         cg = Codegen(field_args, halo, rank_shape)
         body = cg.emit_statements(map_dict, tmp_instructions)
-        ptr_params = ", ".join(
-            f"real* __restrict__ {fa.name}" for fa in self.field_args)
-        dbl_params = ", ".join(f"double {c}" for c, _ in cg.scalars)
-        params = ", ".join(x for x in (ptr_params, dbl_params) if x)
-        src = ELEMENTWISE_TEMPLATE.format(
+        params = self._declare_fields(cg, field_args, "real*")
+        self._build(ELEMENTWISE_TEMPLATE.format(
             defines=geometry_defines(halo, rank_shape,
                                      rtype=_RTYPE[dtype])
-            + _tile_defines(tile, rank_shape),
-            preamble=PREAMBLE, name=name, params=params, body=body)
-        self.source = src
-        self.scalar_keys = [k for _, k in cg.scalars]
-        self.key = ext().jit_compile(src, name)
-        self.grid = _tile_grid(tile, rank_shape)
-        self.block = tile[0] * tile[1]
-
-    def __call__(self, env):
-        ptrs = []
-        for fa in self.field_args:
-            t = _check_tensor(fa.name, env[fa.name])
-            if t.dtype != self.dtype:
-                raise TypeError(
-                    f"argument {fa.name} has dtype {t.dtype}, kernel "
-                    f"compiled for {self.dtype}")
-            ptrs.append(t.data_ptr())
-        doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
-        ext().jit_launch(self.key, self.grid[0], self.grid[1],
-                         self.grid[2], self.block, 1, 1, 0, _stream(),
-                         ptrs, [], doubles)
+            + _tile_defines(tile),
+            preamble=PREAMBLE, name=name, params=params, body=body),
+            name, compile)
+        self._tiled(tile, rank_shape)
 
 
 def get_elementwise_kernel(map_dict, tmp_instructions, field_args,
@@ -273,23 +470,22 @@ class _StencilCodegen(Codegen):
         return super().field_access(f, outer_idx)
 
 
-class JitStencil:
+class JitStencil(_JitKernel):
     """Compiled LDS-staged stencil map (see STENCIL_TEMPLATE)."""
 
     SBZ, SBY = 32, 8
 
     def __init__(self, map_dict, tmp_instructions, field_args,
                  scalar_names, halo, rank_shape, name="stencil_map",
-                 xchunk=32, dtype=torch.float64):
+                 xchunk=32, dtype=torch.float64, compile=True):
         from pystella_amd.field import (
             Field, Subscript, iter_exprs, walk_expr)
         self.rank_shape = tuple(rank_shape)
         self.dtype = dtype
-        self.field_args = [fa for fa in field_args if fa.spatial]
         h = max(halo) if isinstance(halo, (tuple, list)) else halo
 
         # classify padded-field reads by shift pattern
-        padded = {fa.name for fa in self.field_args if fa.padded}
+        padded = {fa.name for fa in _spatial(field_args) if fa.padded}
         read_yz = set()      # (name, lin) with a (sy|sz)!=0 read
         read_x = set()       # (name, lin) with a pure-x != 0 read
         stores = set()       # components written (never prefetch)
@@ -366,42 +562,19 @@ class JitStencil:
                 f"            r_{nm}_{lin}[p] = r_{nm}_{lin}[p + 1];")
 
         body = cg.emit_statements(map_dict, tmp_instructions)
-        ptr_params = ", ".join(
-            f"real* __restrict__ {fa.name}" for fa in self.field_args)
-        dbl_params = ", ".join(f"double {c}" for c, _ in cg.scalars)
-        params = ", ".join(x for x in (ptr_params, dbl_params) if x)
+        params = self._declare_fields(cg, field_args, "real*")
         defines = geometry_defines(halo, rank_shape, rtype=_RTYPE[dtype])
         defines += (f"#define SBZ {sbz}\n#define SBY {sby}\n"
                     f"#define SXCHUNK {xchunk}\n")
-        src = STENCIL_TEMPLATE.format(
+        self._build(STENCIL_TEMPLATE.format(
             defines=defines, preamble=PREAMBLE, name=name, params=params,
             lds_decls="\n".join(lds_decls),
             stage="\n".join(stage),
             ring_init="\n".join(ring_init),
             ring_load="\n".join(ring_load),
             ring_shift="\n".join(ring_shift),
-            body=body)
-        self.source = src
-        self.scalar_keys = [k for _, k in cg.scalars]
-        self.key = ext().jit_compile(src, name)
-        nx, ny, nz = rank_shape
-        self.grid = ((nz + sbz - 1) // sbz, (ny + sby - 1) // sby,
-                     (nx + xchunk - 1) // xchunk)
-        self.block = sbz * sby
-
-    def __call__(self, env):
-        ptrs = []
-        for fa in self.field_args:
-            t = _check_tensor(fa.name, env[fa.name])
-            if t.dtype != self.dtype:
-                raise TypeError(
-                    f"argument {fa.name} has dtype {t.dtype}, kernel "
-                    f"compiled for {self.dtype}")
-            ptrs.append(t.data_ptr())
-        doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
-        ext().jit_launch(self.key, self.grid[0], self.grid[1],
-                         self.grid[2], self.block, 1, 1, 0, _stream(),
-                         ptrs, [], doubles)
+            body=body), name, compile)
+        self._tiled((sbz, sby, xchunk), rank_shape)
 
 
 def get_stencil_kernel(map_dict, tmp_instructions, field_args,
@@ -449,21 +622,22 @@ extern "C" __global__ __launch_bounds__(TBZ * TBY) void {name}(
 """
 
 
-class JitStageReduction:
+class JitStageReduction(_PartialsKernel):
     """Fused per-site map + multi-quantity reduction of the pre-update
     state.  Emission order per site: temporaries (which include the
     inline Laplacian), reduction accumulation (reads input values), then
     the update stores — so the reducers see the input state even for
     in-place unknowns."""
 
+    _dtype_error = _REDUCTION_DTYPE_ERROR
+
     def __init__(self, map_dict, tmp_instructions, entries, field_args,
                  scalar_names, halo, rank_shape, name="rk_stage_red",
-                 tile=(64, 4, 64)):
+                 tile=(64, 4, 64), compile=True):
         self.rank_shape = tuple(rank_shape)
         self.tile = tile
         self.dtype = torch.float64      # fp64-only kernel (double* params)
         self.entries = entries
-        self.field_args = [fa for fa in field_args if fa.spatial]
         nred = len(entries)
         cg = Codegen(field_args, halo, rank_shape)
 
@@ -477,28 +651,17 @@ class JitStageReduction:
         for lhs, rhs in map_dict.items():
             lines.append(f"{cg.emit(lhs)} = {cg.emit(rhs)};")
 
-        ptr_params = ", ".join(
-            f"double* __restrict__ {fa.name}" for fa in self.field_args)
-        dbl_params = ", ".join(f"double {c}" for c, _ in cg.scalars)
-        params = ", ".join(x for x in (
-            ptr_params, "double* __restrict__ partials", dbl_params) if x)
+        params = self._declare_fields(cg, field_args, "double*",
+                                      [self.PARTIALS])
 
         defines = geometry_defines(halo, rank_shape)
-        defines += _tile_defines(tile, rank_shape)
+        defines += _tile_defines(tile)
         defines += combine
-        src = (STAGERED_TEMPLATE + REDUCTION_TAIL).format(
+        self._build((STAGERED_TEMPLATE + REDUCTION_TAIL).format(
             defines=defines, preamble=PREAMBLE, nred=nred, name=name,
             params=params, init="\n    ".join(init_lines),
-            body="\n            ".join(lines))
-        self.source = src
-        self.scalar_keys = [k for _, k in cg.scalars]
-        self.key = ext().jit_compile(src, name)
-        self.grid = _tile_grid(tile, rank_shape)
-        self.block = tile[0] * tile[1]
-        self.nblk = self.grid[0] * self.grid[1] * self.grid[2]
-        self._partials = None
-
-    # __call__ and _finish are JitReduction's (assigned below it)
+            body="\n            ".join(lines)), name, compile)
+        self._tiled(tile, rank_shape)
 
 
 def get_stage_reduction_kernel(map_dict, tmp_instructions, entries,
@@ -570,6 +733,23 @@ extern "C" __global__ __launch_bounds__(256) void {name}(
 _wrap_cache = {}
 
 
+def wrap_source(rank_shape, h, nf, wrap_axes, dtype):
+    """(kernel name, HIP source) of the wrap of ``wrap_axes`` of ``nf``
+    arrays of ``dtype`` with interior ``rank_shape`` and halo ``h``.
+    Needs no device."""
+    defines = geometry_defines(h, rank_shape, rtype=_RTYPE[dtype])
+    defines += f"#define NF {nf}\n"
+    for ax, nm in enumerate("XYZ"):
+        defines += f"#define WRAP{nm} {1 if ax in wrap_axes else 0}\n"
+    name = _wrap_name(h, nf, wrap_axes)
+    return name, WRAP_TEMPLATE.format(defines=defines, name=name)
+
+
+def _wrap_name(h, nf, wrap_axes):
+    return f"wrap_star_{h}_{nf}_" + "".join(
+        str(int(ax in wrap_axes)) for ax in range(3))
+
+
 def wrap_star(fx, halo, wrap_axes):
     """Periodic wrap of all ``wrap_axes`` halo faces of ``fx`` in one
     kernel launch (star-stencil contract; see WRAP_TEMPLATE)."""
@@ -579,23 +759,13 @@ def wrap_star(fx, halo, wrap_axes):
     nf = 1
     for n in fx.shape[:-3]:
         nf *= n
-    key = (rank_shape, h, nf, tuple(sorted(wrap_axes)), fx.dtype)
-    k = _wrap_cache.get(key)
-    if k is None:
-        defines = geometry_defines(h, rank_shape, rtype=_RTYPE[fx.dtype])
-        defines += f"#define NF {nf}\n"
-        for ax, nm in enumerate("XYZ"):
-            defines += f"#define WRAP{nm} {1 if ax in wrap_axes else 0}\n"
-        name = f"wrap_star_{h}_{nf}_" + "".join(
-            str(int(ax in wrap_axes)) for ax in range(3))
-        src = WRAP_TEMPLATE.format(defines=defines, name=name)
-        key_id = ext().jit_compile(src, name)
-        cells = max((nxp + 2 * h) * (nyp + 2 * h), 1) * 2 * h * nf
-        grid = min(4096, (cells + 255) // 256)
-        _wrap_cache[key] = k = (key_id, grid)
+    kid = _cached_kernel(
+        _wrap_cache, (rank_shape, h, nf, tuple(sorted(wrap_axes)), fx.dtype),
+        _wrap_name(h, nf, wrap_axes),
+        lambda: wrap_source(rank_shape, h, nf, wrap_axes, fx.dtype)[1])
     _check_tensor("f", fx)
-    ext().jit_launch(k[0], k[1], 1, 1, 256, 1, 1, 0, _stream(),
-                     [fx.data_ptr()], [], [])
+    cells = max((nxp + 2 * h) * (nyp + 2 * h), 1) * 2 * h * nf
+    _launch_1d(kid, cells, [fx.data_ptr()], cap=4096)
 
 
 # ---------------------------------------------------------------------------
@@ -681,98 +851,36 @@ def _reducer_pieces(cg, entries, wide_scalars=False):
             f"#define COMBINE(r, a, b) ({combine})\n")
 
 
-def _partials_buffer(kern, dev):
-    """The [nred, nblk] per-block partials buffer that ``kern`` owns,
-    allocated anew when the device or the block count changed."""
-    p = kern._partials
-    if p is None or p.device != dev or p.shape[1] != kern.nblk:
-        p = kern._partials = torch.empty(
-            (len(kern.entries), kern.nblk), dtype=torch.float64,
-            device=dev)
-    return p
-
-
-class JitReduction:
+class JitReduction(_PartialsKernel):
     """Fused multi-quantity grid reduction → per-block partials,
     finished with torch ops + one packed allreduce by the caller."""
 
+    _dtype_error = _REDUCTION_DTYPE_ERROR
+
     def __init__(self, entries, field_args, scalar_names, halo, rank_shape,
-                 name="reduce_map", tile=(64, 4, 64), dtype=None):
-        import torch as _t
-        dtype = dtype if dtype is not None else _t.float64
+                 name="reduce_map", tile=(64, 4, 64), dtype=None,
+                 compile=True):
+        dtype = dtype if dtype is not None else torch.float64
         self.rank_shape = tuple(rank_shape)
         self.tile = tile
         self.dtype = dtype
         self.entries = entries
-        self.field_args = [fa for fa in field_args if fa.spatial]
         nred = len(entries)
         cg = Codegen(field_args, halo, rank_shape)
 
         init_lines, body_lines, combine = _reducer_pieces(cg, entries)
-
-        ptr_params = ", ".join(
-            f"const real* __restrict__ {fa.name}"
-            for fa in self.field_args)
-        dbl_params = ", ".join(f"double {c}" for c, _ in cg.scalars)
-        params = ", ".join(x for x in (
-            ptr_params, "double* __restrict__ partials", dbl_params) if x)
+        params = self._declare_fields(cg, field_args, "const real*",
+                                      [self.PARTIALS])
 
         defines = geometry_defines(halo, rank_shape, rtype=_RTYPE[dtype])
-        defines += _tile_defines(tile, rank_shape)
+        defines += _tile_defines(tile)
         defines += combine
-        src = REDUCTION_TEMPLATE.format(
+        self._build(REDUCTION_TEMPLATE.format(
             defines=defines, preamble=PREAMBLE, nred=nred, name=name,
             params=params,
             init="\n    ".join(init_lines),
-            body="\n        ".join(body_lines))
-        self.source = src
-        self.scalar_keys = [k for _, k in cg.scalars]
-        self.key = ext().jit_compile(src, name)
-        self.grid = _tile_grid(tile, rank_shape)
-        self.block = tile[0] * tile[1]
-        self.nblk = self.grid[0] * self.grid[1] * self.grid[2]
-        self._partials = None
-
-    def _finish(self, dev):
-        """Combine per-block partials on-device, one packed D2H copy."""
-        vals = torch.empty(len(self.entries), dtype=torch.float64,
-                           device=dev)
-        for r, (_, op) in enumerate(self.entries):
-            row = self._partials[r]
-            if op in ("sum", "avg"):
-                vals[r] = row.sum()
-            elif op == "prod":
-                vals[r] = row.prod()
-            elif op == "max":
-                vals[r] = row.max()
-            else:
-                vals[r] = row.min()
-        return vals.cpu().tolist()
-
-    def __call__(self, env):
-        dev = None
-        ptrs = []
-        want = getattr(self, "dtype", None)
-        for fa in self.field_args:
-            t = _check_tensor(fa.name, env[fa.name])
-            if want is None:
-                want = t.dtype
-            elif t.dtype != want:
-                raise TypeError(
-                    f"reduction argument '{fa.name}' has dtype "
-                    f"{t.dtype}, kernel expects {want}")
-            dev = t.device
-            ptrs.append(t.data_ptr())
-        partials = _partials_buffer(self, dev)
-        doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
-        ext().jit_launch(self.key, self.grid[0], self.grid[1],
-                         self.grid[2], self.block, 1, 1, 0, _stream(),
-                         ptrs + [partials.data_ptr()], [], doubles)
-        return self._finish(dev)
-
-
-JitStageReduction.__call__ = JitReduction.__call__
-JitStageReduction._finish = JitReduction._finish
+            body="\n        ".join(body_lines)), name, compile)
+        self._tiled(tile, rank_shape)
 
 
 def get_reduction_kernel(entries, field_args, scalar_names, halo,
@@ -842,12 +950,16 @@ extern "C" __global__ __launch_bounds__(256) void {name}(
 _HIST_LDS_DOUBLES = 8192
 
 
-class JitHistogram:
+class JitHistogram(_JitKernel):
     """Simultaneous weighted histograms of fp64 or fp32 fields (``using
     real = double|float``).  Bin values and weights are evaluated in
     the fields' type; each weight is widened to double where it is
     added, and the bins stay float64 whatever the fields are.
     ``compile=False`` only generates ``self.source``."""
+
+    block = 256
+    _dtype_error = ("histogram argument '{name}' has dtype {got}, kernel "
+                    "compiled for {want}")
 
     def __init__(self, pairs, num_bins, field_args, scalar_names, halo,
                  rank_shape, name="hist_map", dtype=None, compile=True):
@@ -856,7 +968,6 @@ class JitHistogram:
         self.num_bins = num_bins
         self.nhist = len(pairs)
         self.dtype = dtype
-        self.field_args = [fa for fa in field_args if fa.spatial]
         cg = Codegen(field_args, halo, rank_shape)
         body = []
         for hh, (bin_expr, weight_expr) in enumerate(pairs):
@@ -867,47 +978,25 @@ class JitHistogram:
                 "(bb >= NBINS ? NBINS - 1 : bb); "
                 "atomicAdd(&lh[%d * NBINS + bb], (double)(%s)); }"
                 % (b, hh, w))
-        ptr_params = ", ".join(
-            f"const real* __restrict__ {fa.name}"
-            for fa in self.field_args)
-        dbl_params = ", ".join(f"double {c}" for c, _ in cg.scalars)
-        params = ", ".join(x for x in (
-            ptr_params, "double* __restrict__ hist", dbl_params) if x)
+        params = self._declare_fields(cg, field_args, "const real*",
+                                      ["double* __restrict__ hist"])
         template = (HISTOGRAM_TEMPLATE
                     if self.nhist * num_bins <= _HIST_LDS_DOUBLES
                     else HISTOGRAM_GLOBAL_TEMPLATE)
-        src = template.format(
+        self._build(template.format(
             defines=geometry_defines(halo, rank_shape,
                                      rtype=_RTYPE[dtype]),
             preamble=PREAMBLE,
             nhist=self.nhist, nbins=num_bins, name=name, params=params,
-            body="\n        ".join(body))
-        self.source = src
-        self.scalar_keys = [k for _, k in cg.scalars]
-        # compile=False: source only (inspectable without a device)
-        self.key = ext().jit_compile(src, name) if compile else None
-        total = int(np.prod(rank_shape))
-        self.grid = min((total + 255) // 256, 1024)
+            body="\n        ".join(body)), name, compile)
+        self.grid = _blocks_1d(int(np.prod(rank_shape)), 1024)
 
     def __call__(self, env):
-        if self.key is None:
-            raise RuntimeError(
-                "JitHistogram was built with compile=False (source only)")
-        ptrs = []
-        dev = None
-        for fa in self.field_args:
-            t = _check_tensor(fa.name, env[fa.name])
-            if t.dtype != self.dtype:
-                raise TypeError(
-                    f"histogram argument '{fa.name}' has dtype "
-                    f"{t.dtype}, kernel compiled for {self.dtype}")
-            dev = t.device
-            ptrs.append(t.data_ptr())
+        ptrs, dev = self._pointers(env)
         hist = torch.zeros((self.nhist, self.num_bins),
                            dtype=torch.float64, device=dev)
-        doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
-        ext().jit_launch(self.key, self.grid, 1, 1, 256, 1, 1, 0,
-                         _stream(), ptrs + [hist.data_ptr()], [], doubles)
+        self._launch(self.key, (self.grid, 1, 1), env,
+                     ptrs + [hist.data_ptr()])
         return hist.cpu().numpy()
 
 
@@ -980,32 +1069,22 @@ _spectra_bin_cache = {}
 
 
 def _spectra_bin(fk, wbase, bidx, num_bins, ctype):
-    _check_tensor("fk", fk)
-    if fk.dtype != getattr(torch, ctype):
-        raise TypeError(f"argument fk has dtype {fk.dtype}; this binning "
-                        f"kernel takes {ctype}")
+    _check_arg("fk", fk, getattr(torch, ctype),
+               f"; this binning kernel takes {ctype}")
     n = fk.numel()
     for name, t, dtype in (("wbase", wbase, torch.float64),
                            ("bidx", bidx, torch.int32)):
-        _check_tensor(name, t)
-        if t.dtype != dtype:
-            raise TypeError(f"argument {name} has dtype {t.dtype}, "
-                            f"expected {dtype}")
-        if t.numel() != n:
-            raise ValueError(f"argument {name} has {t.numel()} elements, "
-                             f"fk has {n}")
+        _check_arg(name, t, dtype, f", expected {dtype}",
+                   numel=(n, "fk has"))
     # the complex128 key is the bare bin count, as it always was
-    key = num_bins if ctype == "complex128" else (num_bins, ctype)
-    k = _spectra_bin_cache.get(key)
-    if k is None:
-        src = spectra_bin_source(num_bins, ctype)
-        kid = ext().jit_compile(src, _SPECTRA_BIN_FORMS[ctype][0])
-        _spectra_bin_cache[key] = k = kid
+    kid = _cached_kernel(
+        _spectra_bin_cache,
+        num_bins if ctype == "complex128" else (num_bins, ctype),
+        _SPECTRA_BIN_FORMS[ctype][0],
+        lambda: spectra_bin_source(num_bins, ctype))
     hist = torch.zeros(num_bins, dtype=torch.float64, device=fk.device)
-    grid = min(4096, (n + 255) // 256)
-    ext().jit_launch(k, grid, 1, 1, 256, 1, 1, 0, _stream(),
-                     [fk.data_ptr(), wbase.data_ptr(),
-                      bidx.data_ptr(), hist.data_ptr()], [n], [])
+    _launch_1d(kid, n, [fk.data_ptr(), wbase.data_ptr(), bidx.data_ptr(),
+                        hist.data_ptr()], [n], cap=4096)
     return hist
 
 
@@ -1217,10 +1296,7 @@ def projector_source(op, kshape, times_abs_k=False, ctype="complex128"):
     elem, ldst = _PROJECTOR_LDST[ctype]
     params = ",\n    ".join(f"{elem}* __restrict__ {n}" for n in names)
     head = (f"#define TIMES_ABS_K {1 if times_abs_k else 0}\n"
-            f"#define NKX {kshape[0]}\n"
-            f"#define NKY {kshape[1]}\n"
-            f"#define NKZ {kshape[2]}\n"
-            "#define VOLK ((long)NKX * NKY * NKZ)\n")
+            + _kshape_defines(kshape))
     return (head + PROJECTOR_PREAMBLE.replace("%LDST%", ldst)
             + PROJECTOR_KERNEL.format(
                 name=_proj_kernel_name(op, ctype), params=params,
@@ -1232,15 +1308,11 @@ def _projector_launch(op, kshape, ptrs, eff, times_abs_k, ctype):
     key = (op, tuple(kshape), bool(times_abs_k))
     if ctype != "complex128":
         key += (ctype,)
-    kid = _proj_cache.get(key)
-    if kid is None:
-        src = projector_source(op, kshape, times_abs_k, ctype)
-        kid = ext().jit_compile(src, _proj_kernel_name(op, ctype))
-        _proj_cache[key] = kid
-    vol = int(np.prod(kshape))
-    grid = (vol + 255) // 256
-    ext().jit_launch(kid, grid, 1, 1, 256, 1, 1, 0, _stream(),
-                     list(ptrs) + [e.data_ptr() for e in eff], [], [])
+    kid = _cached_kernel(
+        _proj_cache, key, _proj_kernel_name(op, ctype),
+        lambda: projector_source(op, kshape, times_abs_k, ctype))
+    _launch_1d(kid, int(np.prod(kshape)),
+               list(ptrs) + [e.data_ptr() for e in eff])
 
 
 def projector_op(op, kshape, ptrs, eff, times_abs_k=False):
@@ -1253,13 +1325,8 @@ def projector_op(op, kshape, ptrs, eff, times_abs_k=False):
 
 
 def _c64_tensor(name, t, shape):
-    _check_tensor(name, t)
-    if t.dtype != torch.complex64:
-        raise TypeError(f"argument {name} has dtype {t.dtype}; the "
-                        "complex64 observable kernels take complex64")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"argument {name} has shape {tuple(t.shape)}, "
-                         f"expected {tuple(shape)}")
+    _check_arg(name, t, torch.complex64,
+               "; the complex64 observable kernels take complex64", shape)
 
 
 def _c64_tables(eff, kshape):
@@ -1463,11 +1530,7 @@ def kspace_source(op, kshape, ctype="complex128", **flags):
     Needs no device."""
     ctype = _ctype_name(ctype)
     params, body = _kspace_pieces(op, dict(flags), _KspaceModes(ctype))
-    head = (f"#define NKX {kshape[0]}\n"
-            f"#define NKY {kshape[1]}\n"
-            f"#define NKZ {kshape[2]}\n"
-            "#define VOLK ((long)NKX * NKY * NKZ)\n")
-    return head + KSPACE_KERNEL.format(
+    return _kshape_defines(kshape) + KSPACE_KERNEL.format(
         name=_kspace_kernel_name(op, ctype), params=",\n    ".join(params),
         body="\n    ".join(body))
 
@@ -1476,42 +1539,30 @@ _kspace_cache = {}
 
 
 def _kspace_complex(name, t, kshape=None, ctype="complex128"):
-    _check_tensor(name, t)
-    if t.dtype != getattr(torch, ctype):
-        kernels = ("k-space" if ctype == "complex128"
-                   else f"{ctype} k-space")
-        raise TypeError(f"argument {name} has dtype {t.dtype}; the "
-                        f"{kernels} kernels take {ctype}")
-    if t.dim() != 3 or (kshape is not None and tuple(t.shape) != kshape):
-        raise ValueError(f"argument {name} has shape {tuple(t.shape)}, "
-                         f"expected {kshape or 'a 3-D k-space array'}")
+    """Check a mode array (3-D; of ``kshape`` if given); its shape."""
+    kernels = "k-space" if ctype == "complex128" else f"{ctype} k-space"
+    _check_arg(name, t, getattr(torch, ctype),
+               f"; the {kernels} kernels take {ctype}", kshape,
+               ndim=None if kshape else 3)
     return tuple(t.shape)
 
 
 def _kspace_table(name, t, n):
-    _check_tensor(name, t)
-    if t.dtype != torch.float64:
-        raise TypeError(f"argument {name} has dtype {t.dtype}; the k-space "
-                        "tables are float64")
-    if t.dim() != 1 or t.numel() != n:
-        raise ValueError(f"argument {name} has shape {tuple(t.shape)}, "
-                         f"expected ({n},)")
+    _check_arg(name, t, torch.float64, "; the k-space tables are float64",
+               (n,))
 
 
 def _kspace_launch(op, kshape, ctype, ptrs, doubles, **flags):
     """``flags`` as the entry points normalise them (``outs`` in
     KSPACE_DERIV_OUTS order, ``mu`` an int, ``accumulate`` a bool)."""
-    key = (op, kshape, ctype) + tuple(sorted(flags.items()))
-    kid = _kspace_cache.get(key)
-    if kid is None:
-        kid = ext().jit_compile(kspace_source(op, kshape, ctype, **flags),
-                                _kspace_kernel_name(op, ctype))
-        _kspace_cache[key] = kid
+    kid = _cached_kernel(
+        _kspace_cache, (op, kshape, ctype) + tuple(sorted(flags.items())),
+        _kspace_kernel_name(op, ctype),
+        lambda: kspace_source(op, kshape, ctype, **flags))
     vol = int(np.prod(kshape))
     if vol == 0:
         return
-    ext().jit_launch(kid, (vol + 255) // 256, 1, 1, 256, 1, 1, 0, _stream(),
-                     ptrs, [], doubles)
+    _launch_1d(kid, vol, ptrs, doubles=doubles)
 
 
 def _kspace_derivs(ctype, fk, outs, k1, k2, inv_n):
@@ -1625,11 +1676,7 @@ def kspace_poisson_c64(rhok, sol, ex, ey, ez, inv_n, m_squared):
 # contraction here: a map's result is defined to a tolerance, not to the
 # bits of a torch chain.
 
-KSPACE_MAP_TEMPLATE = """#define NKX {nkx}
-#define NKY {nky}
-#define NKZ {nkz}
-#define VOLK ((long)NKX * NKY * NKZ)
-using real = double;
+KSPACE_MAP_TEMPLATE = """{defines}using real = double;
 {preamble}
 extern "C" __global__ __launch_bounds__(256) void {name}(
     {params})
@@ -1664,7 +1711,7 @@ def _kspace_map_dtype(name, dtype):
     return key
 
 
-class JitKspaceMap:
+class JitKspaceMap(_JitKernel):
     """A compiled complex k-space map over k-space ``kshape``.
 
     :arg field_args: the :class:`FieldArg`\\ s of the grid fields and the
@@ -1676,10 +1723,14 @@ class JitKspaceMap:
     ``compile=False`` only generates ``self.source``.
     """
 
+    block = 256
+    _dtype_error = ("argument {name} has dtype {got}, kernel compiled for "
+                    "{short}")
+
     def __init__(self, map_dict, tmp_instructions, field_args, dtypes,
                  kshape, name="kspace_map", compile=True):
         self.kshape = tuple(int(n) for n in kshape)
-        self.field_args = [fa for fa in field_args if fa.spatial]
+        self.field_args = _spatial(field_args)
         self.dtypes = {fa.name: _kspace_map_dtype(fa.name, dtypes[fa.name])
                        for fa in self.field_args}
         for fa in self.field_args:
@@ -1688,51 +1739,42 @@ class JitKspaceMap:
                                 f"{self.dtypes[fa.name]}; tables are real")
         cg = KspaceCodegen(field_args, self.dtypes)
         body = cg.emit_statements(map_dict, tmp_instructions)
-        params = []
-        for fa in self.field_args:
-            elem = KSPACE_DTYPES[self.dtypes[fa.name]][0]
+
+        def pointer(name):
+            elem = KSPACE_DTYPES[self.dtypes[name]][0]
             # a stored array may be read too, under the one name
-            params.append(f"{elem}* {fa.name}" if fa.name in cg.stored
-                          else f"const {elem}* __restrict__ {fa.name}")
-        params += [f"const double {c}" for c, _ in cg.scalars]
+            return (f"{elem}* {name}" if name in cg.stored
+                    else f"const {elem}* __restrict__ {name}")
+
+        params = self._declare(cg, [fa.name for fa in self.field_args],
+                               pointer, scalar="const double", sep=",\n    ")
         vol = int(np.prod(self.kshape))
-        self.source = KSPACE_MAP_TEMPLATE.format(
-            nkx=self.kshape[0], nky=self.kshape[1], nkz=self.kshape[2],
-            preamble=PREAMBLE + KSPACE_PREAMBLE, name=name,
-            params=",\n    ".join(params),
-            decode=_KSPACE_MAP_DECODE[vol < 2**31] if cg.uses_axes else "",
-            body="\n    ".join(body))
         self.stored = frozenset(cg.stored)
-        self.scalar_keys = [k for _, k in cg.scalars]
-        self.blocks = (vol + 255) // 256
-        self.key = ext().jit_compile(self.source, name) if compile else None
+        self.blocks = _blocks_1d(vol)
+        self._build(KSPACE_MAP_TEMPLATE.format(
+            defines=_kshape_defines(self.kshape),
+            preamble=PREAMBLE + KSPACE_PREAMBLE, name=name, params=params,
+            decode=_KSPACE_MAP_DECODE[vol < 2**31] if cg.uses_axes else "",
+            body="\n    ".join(body)), name, compile)
+
+    def _arg_dtype(self, name):
+        return getattr(torch, self.dtypes[name])
 
     def __call__(self, env):
         """Launch on ``env``'s tensors, which the caller has checked
         against ``kshape`` and ``dtypes``."""
-        if self.key is None:
-            raise RuntimeError(
-                "JitKspaceMap was built with compile=False (source only)")
-        ptrs = []
+        ptrs, _ = self._pointers(env)
         for fa in self.field_args:
-            t = _check_tensor(fa.name, env[fa.name])
-            if str(t.dtype) != "torch." + self.dtypes[fa.name]:
-                raise TypeError(
-                    f"argument {fa.name} has dtype {t.dtype}, kernel "
-                    f"compiled for {self.dtypes[fa.name]}")
             want = int(np.prod(fa.outer_shape, dtype=np.int64)) \
                 * int(np.prod(self.kshape)) if fa.axis is None \
                 else self.kshape[fa.axis]
-            if t.numel() != want:
+            if env[fa.name].numel() != want:
                 raise ValueError(
-                    f"argument {fa.name} has {t.numel()} elements, the "
-                    f"kernel addresses {want}")
-            ptrs.append(t.data_ptr())
+                    f"argument {fa.name} has {env[fa.name].numel()} "
+                    f"elements, the kernel addresses {want}")
         if self.blocks == 0:
             return
-        doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
-        ext().jit_launch(self.key, self.blocks, 1, 1, 256, 1, 1, 0,
-                         _stream(), ptrs, [], doubles)
+        self._launch(self.key, (self.blocks, 1, 1), env, ptrs)
 
 
 # ---------------------------------------------------------------------------
@@ -1882,16 +1924,6 @@ def rayleigh_source(kshape, grid_shape, *, wkb, is_real, random, ctype):
 _rayleigh_cache = {}
 
 
-def _rayleigh_real(name, t, kshape):
-    _check_tensor(name, t)
-    if t.dtype != torch.float64:
-        raise TypeError(f"argument {name} has dtype {t.dtype}; the "
-                        "Rayleigh kernel reads float64")
-    if tuple(t.shape) != kshape:
-        raise ValueError(f"argument {name} has shape {tuple(t.shape)}, "
-                         f"expected {kshape}")
-
-
 def rayleigh_modes(fk, dfk, sqrt_power, omega, tables, grid_shape, seed,
                    draw, hubble=0., *, is_real, random=True):
     """One launch: fill ``fk`` (and, for the WKB pair, ``dfk``) with the
@@ -1906,39 +1938,24 @@ def rayleigh_modes(fk, dfk, sqrt_power, omega, tables, grid_shape, seed,
     """
     from pystella_amd.fourier.philox import check_draw, check_seed
     wkb = dfk is not None
-    _check_tensor("fk", fk)
-    if fk.dtype not in (torch.complex128, torch.complex64):
-        raise TypeError(f"argument fk has dtype {fk.dtype}; the Rayleigh "
-                        "kernel stores complex128 or complex64")
-    if fk.dim() != 3:
-        raise ValueError(f"argument fk has shape {tuple(fk.shape)}, "
-                         "expected a 3-D k-space array")
+    _check_arg("fk", fk, (torch.complex128, torch.complex64),
+               "; the Rayleigh kernel stores complex128 or complex64",
+               ndim=3)
     kshape = tuple(fk.shape)
     if wkb:
-        _check_tensor("dfk", dfk)
-        if dfk.dtype != fk.dtype:
-            raise TypeError(f"argument dfk has dtype {dfk.dtype}, fk has "
-                            f"{fk.dtype}")
-        if tuple(dfk.shape) != kshape:
-            raise ValueError(f"argument dfk has shape {tuple(dfk.shape)}, "
-                             f"expected {kshape}")
+        _check_arg("dfk", dfk, fk.dtype, f", fk has {fk.dtype}", kshape)
         if dfk.data_ptr() == fk.data_ptr() and fk.numel():
             raise ValueError("output dfk aliases fk")
     if (omega is not None) != wkb:
         raise ValueError("omega goes with dfk: pass both or neither")
-    _rayleigh_real("sqrt_power", sqrt_power, kshape)
-    if wkb:
-        _rayleigh_real("omega", omega, kshape)
+    for name, t in (("sqrt_power", sqrt_power), ("omega", omega))[:1 + wkb]:
+        _check_arg(name, t, torch.float64,
+                   "; the Rayleigh kernel reads float64", kshape)
     if len(tables) != 3 or len(grid_shape) != 3:
         raise ValueError("tables and grid_shape have three entries")
     for ax, t, n in zip("xyz", tables, kshape):
-        _check_tensor(f"tables[{ax}]", t)
-        if t.dtype != torch.int32:
-            raise TypeError(f"argument tables[{ax}] has dtype {t.dtype}; "
-                            "the index tables are int32")
-        if t.dim() != 1 or t.numel() != n:
-            raise ValueError(f"argument tables[{ax}] has shape "
-                             f"{tuple(t.shape)}, expected ({n},)")
+        _check_arg(f"tables[{ax}]", t, torch.int32,
+                   "; the index tables are int32", (n,))
     grid_shape = tuple(int(n) for n in grid_shape)
     if min(grid_shape) < 1 or max(grid_shape) >= 2**31:
         raise ValueError(f"grid_shape {grid_shape} is out of range")
@@ -1951,11 +1968,9 @@ def rayleigh_modes(fk, dfk, sqrt_power, omega, tables, grid_shape, seed,
                  ctype=fk.dtype)
     key = (kshape, grid_shape) + tuple(sorted(flags.items(),
                                               key=lambda kv: kv[0]))
-    kid = _rayleigh_cache.get(key)
-    if kid is None:
-        kid = ext().jit_compile(
-            rayleigh_source(kshape, grid_shape, **flags), "rayleigh_modes")
-        _rayleigh_cache[key] = kid
+    kid = _cached_kernel(
+        _rayleigh_cache, key, "rayleigh_modes",
+        lambda: rayleigh_source(kshape, grid_shape, **flags))
 
     def signed(w):
         return w - 2**32 if w >= 2**31 else w
@@ -1965,9 +1980,9 @@ def rayleigh_modes(fk, dfk, sqrt_power, omega, tables, grid_shape, seed,
     if wkb:
         ptrs.append(omega.data_ptr())
     ptrs += [t.data_ptr() for t in tables]
-    ext().jit_launch(kid, (vol + 255) // 256, 1, 1, 256, 1, 1, 0, _stream(),
-                     ptrs, [signed(seed & 0xffffffff), signed(seed >> 32),
-                            draw], [float(hubble)] if wkb else [])
+    _launch_1d(kid, vol, ptrs,
+               [signed(seed & 0xffffffff), signed(seed >> 32), draw],
+               [float(hubble)] if wkb else [])
 
 
 # ---------------------------------------------------------------------------
@@ -2228,13 +2243,10 @@ def _mg_launch(kind, f1, f2, coefs, key, halo, correct):
             f"mg_{kind}: f1 {tuple(f1.shape)} {f1.dtype} and f2 "
             f"{tuple(f2.shape)} {f2.dtype} are not a contiguous, "
             f"non-overlapping fine/coarse pair at halo {halo}")
-    key = (kind, key, halo, f1.dtype, correct)
-    kid = _mg_cache.get(key)
-    if kid is None:
-        kid = ext().jit_compile(
-            mg_transfer_source(kind, coefs, halo, f1.dtype, correct),
-            _mg_kernel_name(kind, correct))
-        _mg_cache[key] = kid
+    kid = _cached_kernel(
+        _mg_cache, (kind, key, halo, f1.dtype, correct),
+        _mg_kernel_name(kind, correct),
+        lambda: mg_transfer_source(kind, coefs, halo, f1.dtype, correct))
     n2 = [s - 2 * halo for s in f2.shape[-3:]]
     nouter = 1
     for s in f2.shape[:-3]:
@@ -2380,32 +2392,6 @@ def _real_name(dtype):
     if dtype not in _RTYPE:
         raise TypeError(f"unsupported kernel dtype {dtype}")
     return "double" if dtype == torch.float64 else "real"
-
-
-def _kernel_ptrs(kern, env):
-    """(pointers, device) of a ring kernel's array arguments, each
-    checked against the kernel's dtype (the device-state scalar buffer
-    is float64 whatever the fields are).  The kernel would read a
-    buffer of another dtype as its own type: garbage, and past the end
-    of a narrower one."""
-    if kern.key is None:
-        raise RuntimeError(
-            f"{type(kern).__name__} was built with compile=False "
-            "(source only) and cannot be launched")
-    for n in kern.ptr_names:
-        want = torch.float64 if n == "state" and kern.state_map \
-            else kern.dtype
-        t = env[n]
-        if isinstance(t, torch.Tensor) and t.dtype != want:
-            raise TypeError(
-                f"argument {n} has dtype {t.dtype}, kernel "
-                f"compiled for {want}")
-    ptrs, dev = [], None
-    for n in kern.ptr_names:
-        t = _check_tensor(n, env[n])
-        dev = t.device
-        ptrs.append(t.data_ptr())
-    return ptrs, dev
 
 
 def _lapc0_define(lapc0, dtype):
@@ -2643,26 +2629,34 @@ def _march_pieces(f_name, halo, dx, periodic, dtype):
     ), _lapc0_define(lapc0, dtype)
 
 
-def _ring_params(cg, field_args, f_name, lap_name, R, store_lap=False,
-                 state=False, ints=None):
-    """(pointer names, their field args, parameter list) of a ring
-    kernel: stencil field first, the Laplacian if stored, the other
-    spatial fields sorted, the device-state buffer if any, partials,
-    ints, then the run-time scalars ``cg`` collected so far."""
-    ptr_names = [f_name] + ([lap_name] if store_lap else []) + sorted(
-        fa.name for fa in field_args
-        if fa.spatial and fa.name not in (f_name, lap_name))
-    by_name = {fa.name: fa for fa in field_args}
-    ptr_args = [by_name[n] for n in ptr_names if n in by_name]
-    params = [f"{R}* __restrict__ {n}" for n in ptr_names]
-    if state:
-        ptr_names.append("state")
-        params.append("const double* __restrict__ state")
-    params.append("double* __restrict__ partials")
-    if ints:
-        params.append(ints)
-    params += [f"double {c}" for c, _ in cg.scalars]
-    return ptr_names, ptr_args, ", ".join(params)
+class _RingKernel(_PartialsKernel):
+    """Host side of the register-ring Laplacian kernels."""
+
+    state_map = None
+
+    def _declare_ring(self, cg, field_args, f_name, lap_name, R,
+                      store_lap=False, ints=()):
+        """The parameter list of a ring kernel: stencil field first, the
+        Laplacian if stored, the other spatial fields sorted, the
+        device-state buffer if any, partials, ints, then the run-time
+        scalars ``cg`` collected so far."""
+        names = [f_name] + ([lap_name] if store_lap else []) + sorted(
+            fa.name for fa in field_args
+            if fa.spatial and fa.name not in (f_name, lap_name))
+        by_name = {fa.name: fa for fa in field_args}
+        self.field_args = [by_name[n] for n in names if n in by_name]
+        if self.state_map:
+            names.append("state")
+        return self._declare(
+            cg, names,
+            lambda n: ("const double* __restrict__ state" if n == "state"
+                       else f"{R}* __restrict__ {n}"),
+            [self.PARTIALS] + list(ints))
+
+    def _arg_dtype(self, name):
+        # the device-state scalar buffer is float64 whatever the fields are
+        return torch.float64 if name == "state" and self.state_map \
+            else self.dtype
 
 
 class _LapCodegen(Codegen):
@@ -2699,7 +2693,7 @@ class _LapCodegen(Codegen):
         return super().field_access(f, outer_idx)
 
 
-class JitLapReduction:
+class JitLapReduction(_RingKernel):
     """Fused lap-stencil + multi-quantity reduction (see module note)."""
 
     def __init__(self, entries, field_args, scalar_names, halo, rank_shape,
@@ -2709,7 +2703,6 @@ class JitLapReduction:
         self.rank_shape = tuple(rank_shape)
         self.tile = tile
         self.dtype = dtype
-        self.state_map = None
         self.store_lap = store_lap
         self.entries = entries
         self.nf = nf
@@ -2722,38 +2715,21 @@ class JitLapReduction:
             cg.one = "real(1.0)"
         init_lines, body_lines, combine = _reducer_pieces(
             cg, entries, wide_scalars=R == "real")
-        self.ptr_names, self.field_args, params = _ring_params(
-            cg, field_args, f_name, lap_name, R, store_lap=store_lap)
+        params = self._declare_ring(cg, field_args, f_name, lap_name, R,
+                                    store_lap=store_lap)
 
         defines = geometry_defines(halo, rank_shape, rtype=_RTYPE[dtype])
-        defines += _tile_defines(tile, rank_shape)
+        defines += _tile_defines(tile)
         defines += combine + lapc0
         defines += f"#define STORE_LAP {1 if store_lap else 0}\n"
-        src = _ring_source(dict(
+        self._build(_ring_source(dict(
             defines=defines, preamble=PREAMBLE, nred=len(entries), nf=nf,
             bounds="TBZ * TBY", name=name, params=params,
             init="\n    ".join(init_lines),
             store_lap=_STORE_LAP.format(lapname=lap_name),
-            body="\n            ".join(body_lines), **march), _FORM_GRID)
-        self.source = src
-        self.scalar_keys = [k for _, k in cg.scalars]
-        # compile=False: source only (inspectable without a device)
-        self.key = ext().jit_compile(src, name) if compile else None
-        self.grid = _tile_grid(tile, rank_shape)
-        self.block = tile[0] * tile[1]
-        self.nblk = self.grid[0] * self.grid[1] * self.grid[2]
-        self._partials = None
-
-    _finish = JitReduction._finish
-
-    def __call__(self, env):
-        ptrs, dev = _kernel_ptrs(self, env)
-        partials = _partials_buffer(self, dev)
-        doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
-        ext().jit_launch(self.key, self.grid[0], self.grid[1],
-                         self.grid[2], self.block, 1, 1, 0, _stream(),
-                         ptrs + [partials.data_ptr()], [], doubles)
-        return self._finish(dev)
+            body="\n            ".join(body_lines), **march), _FORM_GRID),
+            name, compile)
+        self._tiled(tile, rank_shape)
 
 
 class _NTLapCodegen(_LapCodegen):
@@ -2866,7 +2842,7 @@ def _state_prologue(state_map, R):
     return lines
 
 
-class JitLapStage:
+class JitLapStage(_RingKernel):
     """Ring-buffer RK stage kernel fused with input-state reductions:
     the stencil field marches along x through a per-thread register ring
     (one new load per site instead of 4h+1), the Laplacian is formed in
@@ -2890,8 +2866,7 @@ class JitLapStage:
 
     @classmethod
     def pick_tile(cls, rank_shape):
-        import os as _os
-        env = _os.environ.get("PYSTELLA_TILE")
+        env = os.environ.get("PYSTELLA_TILE")
         if env:
             try:
                 tile = tuple(int(x) for x in env.split(","))
@@ -2955,14 +2930,14 @@ class JitLapStage:
         lines, acc_init, combine = _stage_site_body(
             cg, R, tmp_items, entries, list(map_dict.items()), preloads,
             nt)
-        self.ptr_names, self.field_args, params = _ring_params(
-            cg, field_args, f_name, lap_name, R, state=bool(state_map),
-            ints="const int k0b, const int k1b, const int j0b, "
-                 "const int j1b, const int i0b, const int i1b, "
-                 "const int nblkT, const int bid0")
+        params = self._declare_ring(
+            cg, field_args, f_name, lap_name, R,
+            ints=["const int k0b, const int k1b, const int j0b, "
+                  "const int j1b, const int i0b, const int i1b, "
+                  "const int nblkT, const int bid0"])
 
         defines = geometry_defines(halo, rank_shape, rtype=_RTYPE[dtype])
-        defines += _tile_defines(tile, rank_shape)
+        defines += _tile_defines(tile)
         defines += f"#define MINW {min_waves}\n"
         defines += combine + lapc0
         # everything but the form: the shell form is rendered per set
@@ -2972,20 +2947,10 @@ class JitLapStage:
             bounds="TBZ * TBY, MINW", name=name, params=params,
             init="\n    ".join(_state_prologue(state_map, R) + acc_init),
             store_lap="", body="\n            ".join(lines), **march)
-        src = _ring_source(self._parts, _FORM_BOX)
         self._shell_cache = {}
-        self.source = src
-        self.scalar_keys = [k for _, k in cg.scalars]
-        # compile=False: source only (``.source``, ``shell_source``),
-        # inspectable without a device; such a kernel cannot be launched
-        self._compile = compile
-        self.key = ext().jit_compile(src, name) if compile else None
-        self.grid = _tile_grid(tile, rank_shape)
-        self.block = tile[0] * tile[1]
-        self.nblk = self.grid[0] * self.grid[1] * self.grid[2]
-        self._partials = None
-
-    _finish = JitReduction._finish
+        # compile=False leaves ``.source`` and ``shell_source``
+        self._build(_ring_source(self._parts, _FORM_BOX), name, compile)
+        self._tiled(tile, rank_shape)
 
     def _box_geometry(self, box):
         """(grid, ints-prefix) for a sub-box launch; box =
@@ -3010,11 +2975,8 @@ class JitLapStage:
         cached = self._shell_cache.get(boxes)
         if cached is not None:
             return cached
+        self._require_compiled()
         src, name, total = self._shell_build(boxes)
-        if not self._compile:
-            raise RuntimeError(
-                "JitLapStage was built with compile=False (source "
-                "only) and cannot be launched")
         cached = (ext().jit_compile(src, name), total)
         self._shell_cache[boxes] = cached
         return cached
@@ -3044,42 +3006,27 @@ class JitLapStage:
     def shell_nblk(self, boxes):
         return self._get_shell(tuple(boxes))[1]
 
-    def _launch(self, key, grid, env, ptrs, partials, ints):
-        doubles = [_resolve_scalar(env, k) for k in self.scalar_keys]
-        ext().jit_launch(key, grid[0], grid[1], grid[2], self.block, 1, 1,
-                         self.shmem, _stream(),
-                         ptrs + [partials.data_ptr()], ints, doubles)
-
     def launch_shell(self, env, boxes, partials, bid0, nblk_tot):
         """ONE launch covering every box in ``boxes`` (the rank's
         boundary slabs); per-block partials land flat at ``bid0``."""
-        ptrs, _ = _kernel_ptrs(self, env)
+        ptrs, _ = self._pointers(env)
         kid, total = self._get_shell(tuple(boxes))
-        self._launch(kid, (total, 1, 1), env, ptrs, partials,
+        self._launch(kid, (total, 1, 1), env, ptrs + [partials.data_ptr()],
                      [0, 0, 0, 0, 0, 0, nblk_tot, bid0])
 
     def launch_box(self, env, box, partials, bid0, nblk_tot):
         """Launch over a sub-box, writing this launch's per-block
         partials at column offset ``bid0`` of the shared ``partials``
         buffer [nred, nblk_tot].  Stream-ordered, no host sync."""
-        ptrs, _ = _kernel_ptrs(self, env)
+        ptrs, _ = self._pointers(env)
         grid, ints = self._box_geometry(box)
-        self._launch(self.key, grid, env, ptrs, partials,
+        self._launch(self.key, grid, env, ptrs + [partials.data_ptr()],
                      ints + [nblk_tot, bid0])
 
     def launch_only(self, env):
-        """Full-grid launch without finishing the reduction; returns the
-        raw per-block partials tensor [nred, nblk] (stream-ordered, no
-        host synchronization)."""
-        ptrs, dev = _kernel_ptrs(self, env)
-        partials = _partials_buffer(self, dev)
         nx, ny, nz = self.rank_shape
-        self._launch(self.key, self.grid, env, ptrs, partials,
-                     [0, nz, 0, ny, 0, nx, self.nblk, 0])
-        return partials
-
-    def __call__(self, env):
-        return self._finish(self.launch_only(env).device)
+        return super().launch_only(
+            env, [0, nz, 0, ny, 0, nx, self.nblk, 0])
 
 
 FRIEDMANN_TEMPLATE = """
@@ -3150,10 +3097,9 @@ class JitFriedmann:
 
     def __init__(self, nred, nblk, wt, wp, grid_size, mpl=1.,
                  name="friedmann"):
-        import math as _math
         self.nred = nred
         self.nblk = nblk
-        frw_coef = 4 * _math.pi / 3 / mpl**2
+        frw_coef = 4 * math.pi / 3 / mpl**2
         src = FRIEDMANN_TEMPLATE.format(
             nred=nred, nblk=nblk, name=name,
             wt=", ".join(repr(float(w)) for w in wt),
